@@ -10,17 +10,20 @@ engine construction (device layout + row norms), k-means|| initialisation (initS
 KMeans.fit runs it), ``steps`` Lloyd iterations and the model + summary (trainingCost; clusterSizes is
 lazy, as Spark's). A step = one distributed Lloyd iteration: exact bound-pruned K9r MFMA assign, K10
 incremental f64 sums, RCCL all-reduce of the [k·D sums | k counts | cost] message, K11 update.
---warmup runs an untimed warm-up fit of that many iterations first. The same fit driven on the
-LloydEngine directly, the steady-state step and a forced full step are reported in extra (not the
+--warmup runs an untimed warm-up fit of that many iterations first. A plain run does no more than
+that: set up, warm up, time the fit, print the result line. With --full the same fit driven on the
+LloydEngine directly, the steady-state step and a forced full step are also reported in extra (not the
 headline), and with --data blobs (the headline) also a fit on overlapping blobs (extra.overlap), where
-the bounds prune little. The dataset is ONE fixed table (100M rows total) sharded over the N ranks in
+the bounds prune little. --dump-outputs DIR writes what the timed fit returned (cluster centres, cluster
+sizes, training cost) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for
+output. The dataset is ONE fixed table (100M rows total) sharded over the N ranks in
 row order, so scaling is *strong*: every value is generated from its global row index (utils/synth.py),
 and the fit is partition-invariant, so N = 1, 2, 4, 8 fit the same problem and report the same
 trainingCost bits and cluster sizes (extra.training_cost_hex / cluster_sizes_digest). Data: synthetic
 Gaussian blobs generated on the GPU, bf16 features (no network).
 
 Usage (driver contract):
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -36,6 +39,7 @@ import torch
 
 from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import LloydEngine
 from clustermachinelearningforhospitalnetworks_apache_spark_amd.parallel.comm import Communicator
+from clustermachinelearningforhospitalnetworks_apache_spark_amd.utils.device import gpu_available
 from clustermachinelearningforhospitalnetworks_apache_spark_amd.utils.synth import shard_range
 
 METRIC = "KMeans fit samples/sec (whole node), 100M×256 k=256 at 1/2/4/8 MI355X"
@@ -87,6 +91,26 @@ def _phase(comm, what: str) -> None:
     """Timestamped phase line on rank 0's stderr (where a run's wall time goes: VERDICT r5 weak 9)."""
     if comm is None or comm.rank == 0:
         print(f"[bench +{time.time() - _T0:7.2f}s] {what}", file=sys.stderr, flush=True)
+
+
+_DUMP_LIMIT = 64 << 20  # bytes of all the --dump-outputs files of one run together
+
+
+def _dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array of ``arrays`` as ``path/<name>.npy``, float64 (float32 stays float32). An
+    array over its share of the 64 MB limit is cut to a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = _DUMP_LIMIT // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(12345).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _drop_norm_cache(x: torch.Tensor) -> None:
@@ -154,7 +178,14 @@ def main():
     ap.add_argument("--data", default="blobs", choices=sorted(_DATA),
                     help="blobs = the headline data (separated blobs); overlap = blob centres 8x closer; "
                          "uniform = no cluster structure")
-    ap.add_argument("--no-overlap", action="store_true", help="skip the extra overlap-data fit")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed fit also measure what the headline does not need: the same fit on the "
+                         "engine directly, steady-state / full / from-scratch step times and, on the headline data, "
+                         "the overlap-data fits (all reported in extra)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 or float64, at most "
+                         "64 MB in all); same arguments = same inputs, so two builds compare output for output")
+    ap.add_argument("--no-overlap", action="store_true", help="--full: skip the extra overlap-data fit")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f64"],
                     help="feature dtype of the frame (f32/f64: the reference's Double/Integer columns, fitted at "
                          "source precision by default)")
@@ -197,9 +228,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus and world != 1:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
-    gpu = torch.cuda.is_available()
+    gpu = gpu_available()
     if not gpu:
-        # CPU plumbing run only (no MI355X here): shrink so it finishes.
+        # CPU plumbing run only (no MI355X here, or CML_FORCE_CPU=1): shrink so it finishes.
         args.rows, args.dim, args.k = min(args.rows, 200_000), min(args.dim, 32), min(args.k, 16)
     spark = (SparkSession.builder.appName("bench-kmeans").master("mi355x" if gpu else "local[1]")
              .config("cml.ml.features.dtype", "bf16" if gpu else "float64").getOrCreate())
@@ -231,29 +262,35 @@ def main():
     # the timed region: one whole public-API fit from scratch, bracketed by barrier + device sync
     _phase(comm, "timed fit")
     model, elapsed = _timed(comm, gpu, lambda: api_fit(df, args, seed=42, iters=args.steps))
-    _phase(comm, f"timed fit done ({1000 * elapsed:.1f} ms); engine / step measurements")
+    _phase(comm, f"timed fit done ({1000 * elapsed:.1f} ms)")
     summ = model.summary
     sizes = summ.clusterSizes
     acc = {"api": f"KMeans(k={args.k}, maxIter={args.steps}, tol={args.tol:g}, seed=42).fit(df)",
            "iterations": summ.numIter, "training_cost": summ.trainingCost,
            "training_cost_hex": float(summ.trainingCost).hex(), "cluster_sizes_digest": _digest(sizes),
            "cluster_sizes_minmax": [min(sizes), max(sizes)]}
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed fit holds: the model's centres and its summary
+        _dump_outputs(args.dump_outputs, {"cluster_centers": model.clusterCenters(), "cluster_sizes": sizes,
+                                          "training_cost": [summ.trainingCost]})
     del model, summ
     _drop_norm_cache(x)
 
-    # the same fit on the engine directly (no Estimator layer), then its steady-state and full steps
-    (eng, t_init), eng_s = _timed(comm, gpu, lambda: kmeans_fit(x, args, comm, seed=42, iters=args.steps)[:2])
-    acc["engine_fit_ms"] = round(1000.0 * eng_s, 3)
-    acc["api_over_engine"] = round(elapsed / eng_s, 4) if eng_s > 0 else None
-    acc["accumulate"] = "incremental (exact)" if eng.delta is not None else "full"
-    acc["assign"] = "pruned (exact bounds)" if eng.prune else "full (every row x every centre)"
-    if eng.prune:
-        acc["last_step_prune_rank0"] = eng.prune_stats()
-    acc["precision"] = eng.precision
-    if gpu and eng.gpu:
-        acc.update(_step_rates(eng, comm))
-    del eng
-    _drop_norm_cache(x)
+    if args.full:
+        # the same fit on the engine directly (no Estimator layer), then its steady-state and full steps
+        _phase(comm, "engine / step measurements")
+        (eng, t_init), eng_s = _timed(comm, gpu, lambda: kmeans_fit(x, args, comm, seed=42, iters=args.steps)[:2])
+        acc["engine_fit_ms"] = round(1000.0 * eng_s, 3)
+        acc["api_over_engine"] = round(elapsed / eng_s, 4) if eng_s > 0 else None
+        acc["accumulate"] = "incremental (exact)" if eng.delta is not None else "full"
+        acc["assign"] = "pruned (exact bounds)" if eng.prune else "full (every row x every centre)"
+        if eng.prune:
+            acc["last_step_prune_rank0"] = eng.prune_stats()
+        acc["precision"] = eng.precision
+        if gpu and eng.gpu:
+            acc.update(_step_rates(eng, comm))
+        del eng
+        _drop_norm_cache(x)
     if args.breakdown:
         comm.barrier()
         tb = time.perf_counter()
@@ -272,7 +309,7 @@ def main():
         del eng
         _drop_norm_cache(x)
 
-    if gpu and args.data == "blobs" and args.dtype == "bf16" and not args.no_overlap:
+    if args.full and gpu and args.data == "blobs" and args.dtype == "bf16" and not args.no_overlap:
         # the same public-API fit on overlapping blobs (centres 8x closer), where the exact bounds prune
         # little: the robustness of the headline. Same shape, separate data.
         del df
@@ -388,7 +425,7 @@ def bench_logreg(args):
     import numpy as np
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.optim import lbfgs
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import glm_ops
-    gpu = torch.cuda.is_available()
+    gpu = gpu_available()
     if not gpu:
         args.rows, args.dim = min(args.rows, 200_000), min(args.dim, 32)
     comm = Communicator.from_env(want_gpu=gpu)
@@ -476,6 +513,8 @@ def bench_logreg(args):
                            "seq_len": None, "parallelism": f"dp{W}"},
                 "extra": {"mean_loss": float(loss.item()) / max(opt.steps, 1), "hip_graph": opt.use_graph}}),
                 flush=True)
+            if args.dump_outputs:
+                _dump_outputs(args.dump_outputs, {"coefficients": opt.coef})
         comm.shutdown()
         return
     p0 = np.zeros(d + 1)
@@ -505,6 +544,8 @@ def bench_logreg(args):
                        "parallelism": f"dp{W}"},
             "extra": {"datagen_s": round(gen_s, 3), "scaler_s": round(scaler_s, 3), "final_loss": hist[-1] if hist
                       else None}}), flush=True)
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, {"coefficients": p, "loss_history": hist})
     comm.shutdown()
 
 
@@ -513,8 +554,8 @@ def bench_kmeans_ooc(args):
     live in pinned host memory (more than the HBM budget the pipeline leaves) and every pass over X
     streams them through two device buffers (utils/hoststream.py). Timed: one whole fit (k-means|| init,
     ``--steps`` Lloyd iterations, k = 128, tol = 0). Reports rows·iterations/s like the headline, the
-    streamed bytes, and the copy engine's H2D rate of one pass with no kernels attached."""
-    gpu = torch.cuda.is_available()
+    streamed bytes and, with --full, the copy engine's H2D rate of one pass with no kernels attached."""
+    gpu = gpu_available()
     n, d, k = args.ooc_rows, 512, 128
     if not gpu:
         n = min(n, 50_000)
@@ -558,10 +599,13 @@ def bench_kmeans_ooc(args):
         extra["streamed_GB"] = round(hs.bytes / 1e9, 2)
         extra["passes_over_x"] = hs.passes
         extra["streamed_GB_per_s_in_fit"] = round(hs.bytes / 1e9 / elapsed, 2)
-        for _ in hs.chunks(eng.bounds, timed=True):
-            pass
-        extra["h2d_GB_per_s_copy_only"] = round(hs.last_h2d_gbps() or 0.0, 2)
+        if args.full:  # one more pass over the host rows with no kernels attached
+            for _ in hs.chunks(eng.bounds, timed=True):
+                pass
+            extra["h2d_GB_per_s_copy_only"] = round(hs.last_h2d_gbps() or 0.0, 2)
         extra["chunk_rows"] = hs.chunk_rows
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"cluster_centers": eng.centers, "training_cost": [extra["training_cost"]]})
     print(json.dumps({
         "metric": f"Out-of-core KMeans fit samples/sec, {n / 1e6:g}M x {d} fp8 in pinned host memory, k={k}",
         "value": n * args.steps / elapsed, "unit": "samples/s", "n_gpus": 1 if gpu else 0, "steps": args.steps,
@@ -587,7 +631,7 @@ def bench_pipeline(args):
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.feature import StandardScaler, VectorAssembler
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.pipeline import Pipeline
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
-    gpu = torch.cuda.is_available()
+    gpu = gpu_available()
     n, d = args.rows_per_gpu, (args.dim if args.dim != 256 else 512)
     if not gpu:
         n, d = min(n, 100_000), min(d, 64)
@@ -656,6 +700,11 @@ def bench_pipeline(args):
             "extra": {"datagen_s": round(gen_s, 3), "kmeans_iters": km.summary.numIter,
                       "kmeans_cost": km.summary.trainingCost, "logreg_iters": lr.summary.totalIterations}}),
               flush=True)
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, {"kmeans_cluster_centers": km.clusterCenters(),
+                                              "kmeans_training_cost": [km.summary.trainingCost],
+                                              "logreg_coefficients": lr.coefficients.toArray(),
+                                              "logreg_intercept": [lr.intercept]})
         if os.environ.get("CML_TRACE") == "1":
             print(TRACER.report(), file=sys.stderr, flush=True)
     spark.stop()
@@ -664,8 +713,8 @@ def bench_pipeline(args):
 def bench_csv(args):
     """BASELINE.json config 1 ("KMeans k=5 on 1k x 16 synthetic CSV via local[2] CPU, plumbing"):
     spark.read.csv (native C++ tokenizer/parser, K1) -> VectorAssembler -> KMeans(k=5).fit, on the
-    CPU session (no GPU). One step = the whole read + assemble + fit. The fitted centres are checked
-    against a numpy Lloyd run from the same initial centres (extra.max_center_err)."""
+    CPU session (no GPU). One step = the whole read + assemble + fit. With --full the fitted centres are
+    checked against a numpy Lloyd run from the same initial centres (extra.max_center_err_vs_numpy_lloyd)."""
     import tempfile
 
     import numpy as np
@@ -698,13 +747,17 @@ def bench_csv(args):
     for _ in range(args.steps):
         model = one()
     elapsed = time.perf_counter() - t0
-    # numpy Lloyd oracle from the same data: converged centres must agree (same partition)
     got = np.stack(model.clusterCenters())
-    c = got.copy()
-    for _ in range(50):
-        lab = ((x[:, None, :] - c[None]) ** 2).sum(-1).argmin(1)
-        c = np.stack([x[lab == j].mean(0) if (lab == j).any() else c[j] for j in range(k)])
-    err = float(np.abs(c - got).max())
+    extra = {"kmeans_iters": model.summary.numIter, "training_cost": model.summary.trainingCost}
+    if args.full:
+        # numpy Lloyd oracle from the same data: converged centres must agree (same partition)
+        c = got.copy()
+        for _ in range(50):
+            lab = ((x[:, None, :] - c[None]) ** 2).sum(-1).argmin(1)
+            c = np.stack([x[lab == j].mean(0) if (lab == j).any() else c[j] for j in range(k)])
+        extra["max_center_err_vs_numpy_lloyd"] = float(np.abs(c - got).max())
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"cluster_centers": got, "training_cost": [model.summary.trainingCost]})
     print(json.dumps({
         "metric": "KMeans fit samples/sec, 1k x 16 CSV k=5 via local[2] CPU (read + assemble + fit)",
         "value": n * model.summary.numIter * args.steps / elapsed, "unit": "samples/s", "n_gpus": 0,
@@ -712,8 +765,7 @@ def bench_csv(args):
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp64",
         "data": "synthetic (Gaussian blobs written to CSV)",
         "config": {"model": "KMeans k=5", "global_batch": n, "seq_len": None, "parallelism": "local[2]", "dim": d},
-        "extra": {"kmeans_iters": model.summary.numIter, "training_cost": model.summary.trainingCost,
-                  "max_center_err_vs_numpy_lloyd": err}}), flush=True)
+        "extra": extra}), flush=True)
     spark.stop()
     import shutil
     shutil.rmtree(tmp, ignore_errors=True)

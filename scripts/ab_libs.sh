@@ -15,11 +15,11 @@ for i in $(seq 1 "$R"); do
   for v in A B; do
     cp "ab/lib$v.so" "$L"
     if [[ $W == *h* ]]; then
-      timeout -k 10 300 python3 bench.py --no-overlap > "$O/h_${v}_$i.json" 2> "$O/h_${v}_$i.err" \
+      timeout -k 10 300 python3 bench.py --full --no-overlap > "$O/h_${v}_$i.json" 2> "$O/h_${v}_$i.err" \
         || { tail -5 "$O/h_${v}_$i.err"; exit 1; }
     fi
     if [[ $W == *s* ]]; then
-      CML_COMM_SELF=1 timeout -k 10 300 python3 bench.py --rows 12500000 --warmup 3 --no-overlap \
+      CML_COMM_SELF=1 timeout -k 10 300 python3 bench.py --full --rows 12500000 --warmup 3 --no-overlap \
         > "$O/s_${v}_$i.json" 2> "$O/s_${v}_$i.err" || { tail -5 "$O/s_${v}_$i.err"; exit 1; }
     fi
     python3 - "$O" "$v" "$i" "$W" <<'PY'

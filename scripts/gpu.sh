@@ -54,9 +54,9 @@ final)
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1 \
     || { tail -5 "$O/smoke.log"; exit 1; }
   tail -1 "$O/smoke.log"
-  timeout -k 10 500 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
+  timeout -k 10 500 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
   fit_line "$O/bench.json"
-  timeout -k 10 300 python3 bench.py --rows 10000000 --dim 128 --k 64 --dtype f32 --warmup 1 --steps 20 \
+  timeout -k 10 300 python3 bench.py --full --rows 10000000 --dim 128 --k 64 --dtype f32 --warmup 1 --steps 20 \
     > "$O/cfg2_f32.json" 2> "$O/cfg2_f32.err" || { tail -5 "$O/cfg2_f32.err"; exit 1; }
   fit_line "$O/cfg2_f32.json"
   CML_TRACE=1 timeout -k 10 600 python3 bench.py --workload pipeline --steps 2 --warmup 1 > "$O/pipe.json" \
@@ -86,7 +86,7 @@ profile)
   ;;
 shard)
   export CML_COMM_SELF=1
-  timeout -k 10 300 python3 bench.py --rows 12500000 --warmup 3 --no-overlap --breakdown "$@" > "$O/shard.json" \
+  timeout -k 10 300 python3 bench.py --full --rows 12500000 --warmup 3 --no-overlap --breakdown "$@" > "$O/shard.json" \
     2> "$O/shard.err" || { tail -5 "$O/shard.err"; exit 1; }
   fit_line "$O/shard.json"
   timeout -k 10 300 rocprofv3 --kernel-trace --runtime-trace --marker-trace -d /tmp/sh -o sh -- python3 bench.py \
@@ -103,9 +103,9 @@ shard)
   ;;
 strong)
   for n in 50000000 25000000 12500000; do
-    timeout -k 10 240 python3 bench.py --rows $n --chunks 2 --steps 20 --warmup 3 --no-overlap > "$O/c2_$n.json" \
+    timeout -k 10 240 python3 bench.py --full --rows $n --chunks 2 --steps 20 --warmup 3 --no-overlap > "$O/c2_$n.json" \
       2> "$O/c2_$n.err" || { tail -5 "$O/c2_$n.err"; exit 1; }
-    CML_COMM_SELF=1 timeout -k 10 240 python3 bench.py --rows $n --steps 20 --warmup 3 --no-overlap \
+    CML_COMM_SELF=1 timeout -k 10 240 python3 bench.py --full --rows $n --steps 20 --warmup 3 --no-overlap \
       > "$O/self_$n.json" 2> "$O/self_$n.err" || { tail -5 "$O/self_$n.err"; exit 1; }
     fit_line "$O/c2_$n.json"
     fit_line "$O/self_$n.json"

@@ -17,8 +17,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(n: int, extra, port: int, timeout: int = 300) -> dict:
+def _run(n: int, extra, port: int, timeout: int = 300, cpu: bool = False) -> dict:
     env = dict(os.environ, CML_COMM_BACKEND="gloo", PYTHONPATH=ROOT)
+    if cpu:  # the CPU plumbing run also where a GPU is visible
+        env["CML_FORCE_CPU"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(n), *extra]
@@ -54,7 +56,7 @@ def test_synth_rows_shards_are_rows_of_one_table():
 
 def test_bench_cpu_same_problem_at_1_2_ranks():
     extra = ["--steps", "3", "--warmup", "0", "--rows", "30000", "--dim", "16", "--k", "8"]
-    _check([_run(n, extra, 29800 + n + os.getpid() % 50) for n in (1, 2)])
+    _check([_run(n, extra, 29800 + n + os.getpid() % 50, cpu=True) for n in (1, 2)])
 
 
 @pytest.mark.gpu
