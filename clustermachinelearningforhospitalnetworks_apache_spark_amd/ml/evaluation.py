@@ -236,7 +236,17 @@ class BinaryClassificationEvaluator(Evaluator):
 
 
 class ClusteringEvaluator(Evaluator):
-    """Silhouette with squared euclidean distance (Spark's default), computed from per-cluster sums."""
+    """Silhouette (Spark's ClusteringEvaluator) from per-cluster statistics: ``distanceMeasure``
+    squaredEuclidean (default) or cosine, optional ``weightCol`` (finite, non-negative, not null; rows of
+    weight 0 count in nothing).
+
+    Every rank computes ``[S | W | Q]`` of its rows, one all-reduce makes them global, every rank scores its
+    rows against them and a second all-reduce adds ``(Σ w s, Σ w)``; a rank without rows joins both. bf16 and
+    e4m3 feature columns on the GPU take the K26 kernels (``ops/silhouette_ops.py``: one gather pass for the
+    statistics, one MFMA pass over X for the score, no n x K matrix and no f64 copy of X) when the padded
+    width and the all-reduced cluster count are inside the kernel's limits; f32 / f64 device columns, CPU
+    frames and anything outside those limits take the reference form at source precision (f64 arithmetic, row
+    chunks of 2^16). An out-of-core (host-resident) feature column takes the reference form on the host."""
     _params = {
         "predictionCol": ("prediction", "prediction column name", str),
         "featuresCol": ("features", "features column name", str),
@@ -251,40 +261,63 @@ class ClusteringEvaluator(Evaluator):
         self._defaultParamMap.pop("weightCol", None)
 
     def _evaluate(self, df) -> float:
-        x = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
-        lab = _col(df, self.getPredictionCol()).to(torch.int64)
-        K = int(df._comm.max_scalar(float(lab.max().item()) if lab.numel() else 0.0)) + 1
-        d = x.shape[1]
-        sums = torch.zeros(K, d, dtype=torch.float64, device=x.device)
-        cnt = torch.zeros(K, dtype=torch.float64, device=x.device)
-        sq = torch.zeros(K, dtype=torch.float64, device=x.device)
-        if lab.numel():
-            from ..ops.group_ops import group_reduce, group_sum_rows  # K25 on the GPU (few clusters)
-            sums = group_sum_rows(lab, x, K)
-            cnt = group_reduce(lab, torch.ones_like(lab, dtype=torch.uint8), K, "sum", floating=True)
-            sq = group_reduce(lab, (x * x).sum(1), K, "sum")
-        msg = torch.cat([sums.reshape(-1), cnt, sq])
-        df._comm.allreduce_(msg)
-        sums = msg[: K * d].reshape(K, d)
-        cnt = msg[K * d: K * d + K]
-        sq = msg[K * d + K:]
-        if lab.numel() == 0:
-            part = torch.zeros(2, dtype=torch.float64, device=x.device)
+        from ..ops import silhouette_ops as SO
+        measure = self.getOrDefault("distanceMeasure")
+        if measure not in ("squaredEuclidean", "cosine"):
+            raise ValueError(f"distanceMeasure must be squaredEuclidean or cosine, got {measure!r}")
+        cosine = measure == "cosine"
+        comm = df._comm
+        x = df._feature_matrix(self.getFeaturesCol())
+        cd = df._column_data(self.getPredictionCol())
+        if cd.is_host:
+            raise TypeError(f"column {self.getPredictionCol()!r} must be numeric")
+        lab = cd.values.reshape(-1).to(x.device)
+        if lab.is_floating_point():
+            lab = lab.to(torch.int64)
+        w = _cluster_weights(df, self.getOrDefault("weightCol"), x.device) if self.isSet("weightCol") else None
+        n, d = int(x.shape[0]), int(x.shape[1])
+        # the label range, agreed over ranks before anything is raised or a path is chosen
+        lo, hi = (int(v) for v in torch.aminmax(lab)) if n else (0, -1)
+        rng = torch.tensor([float(hi), 1.0 if lo < 0 else 0.0], dtype=torch.float64, device=comm.device)
+        comm.allreduce_(rng, op="max")
+        if rng[1].item() > 0:
+            raise ValueError(f"column {self.getPredictionCol()!r} holds negative cluster ids")
+        K = int(rng[0].item()) + 1
+        if K < 1:
+            return float("nan")  # no rows on any rank
+        # one path for every rank: the dtype and the all-reduced K decide, never the local row count
+        fast = False
+        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn):
+            from ..models.kmeans import padded_dim_fp8, to_device_matrix
+            from ..utils.device import padded_dim
+            dp = padded_dim_fp8(d) if x.dtype == torch.float8_e4m3fn else padded_dim(d)
+            fast = SO.kernel_supported(x.dtype, dp, K)
+        if fast:
+            xd = to_device_matrix(x, d)  # a copy only when the layout is not already the kernels'
+            lab = lab if lab.dtype == torch.int32 else lab.to(torch.int32)
+            stats, zero = SO.cluster_stats_device(xd, lab, K, w, cosine)
         else:
-            xx = (x * x).sum(1, keepdim=True)
-            # mean squared distance from each point to every cluster: (N_c|x|² − 2x·S_c + Q_c)/N_c
-            dist = (cnt[None, :] * xx - 2 * x @ sums.T + sq[None, :]) / cnt.clamp(min=1)[None, :]
-            own = dist.gather(1, lab.reshape(-1, 1)).reshape(-1)
-            nc = cnt[lab]
-            a = torch.where(nc > 1, own * nc / (nc - 1).clamp(min=1), torch.zeros_like(own))
-            other = dist.clone()
-            other[torch.arange(len(lab), device=x.device), lab] = float("inf")
-            other[:, cnt == 0] = float("inf")
-            b = other.min(1).values
-            s = torch.where(nc > 1, (b - a) / torch.maximum(a, b).clamp(min=1e-300), torch.zeros_like(a))
-            part = torch.stack([s.sum(), torch.tensor(float(len(lab)), dtype=torch.float64, device=x.device)])
-        df._comm.allreduce_(part)
+            zero = cosine and SO.has_zero_rows(x)
+        if cosine:
+            # a zero-length row on one rank makes every rank raise (nobody is left in the collectives below)
+            flag = torch.tensor([1.0 if bool(zero) else 0.0], dtype=torch.float64, device=comm.device)
+            comm.allreduce_(flag, op="max")
+            if flag.item() > 0:
+                raise ValueError(SO.ZERO_ROW)
+        if not fast:
+            stats = SO.cluster_stats_reference(x, lab, K, w, cosine)
+        stats = comm.allreduce_(stats.to(comm.device)).to(x.device)
+        if fast:
+            part = SO.silhouette_score(xd, lab, stats, w, cosine)
+        else:
+            part = SO.silhouette_reference(x, lab, K, w, cosine, stats=stats)
+        part = comm.allreduce_(part.to(comm.device))
         return float(part[0] / part[1]) if part[1] > 0 else float("nan")
+
+
+def _cluster_weights(df, col, device):
+    from .clustering import _weights  # the validation KMeans applies to its weightCol
+    return _weights(df, col, device)
 
 
 # ------------------------------------------------------------------------- multilabel / ranking

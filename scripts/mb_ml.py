@@ -17,6 +17,11 @@
         the reference workflow's tree fits and transforms (ref.py:130-160) through the public API, each between
         device syncs; the first RF-regression transform also under cProfile
 
+    python scripts/mb_ml.py silhouette [--rows 20000000] [--dim 256] [--k 256] [--dtype bf16|fp8] [--measure M]
+        K26 ClusteringEvaluator kernels on blobs with 90 % true labels: the stats pass (row norms, label sort,
+        label_wsum, W / Q group sums) and the score pass (one MFMA pass over X) separately, best-of-5 ms; M is
+        squaredEuclidean, cosine or both; --evaluate also times ClusteringEvaluator.evaluate end to end
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -348,7 +353,62 @@ def cmd_multinomial(argv):
         del y
 
 
-COMMANDS = {"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_silhouette(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import silhouette_ops as SO
+    ap = argparse.ArgumentParser(prog="mb_ml.py silhouette")
+    ap.add_argument("--rows", type=int, default=20_000_000)
+    ap.add_argument("--dim", type=int, default=256)
+    ap.add_argument("--k", type=int, default=256)
+    ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--measure", choices=["squaredEuclidean", "cosine", "both"], default="both")
+    ap.add_argument("--evaluate", action="store_true", help="also time ClusteringEvaluator.evaluate end to end")
+    a = ap.parse_args(argv)
+    n, d, k = a.rows, a.dim, a.k
+    dt = torch.float8_e4m3fn if a.dtype == "fp8" else torch.bfloat16
+    g = torch.Generator(device="cuda").manual_seed(1)
+    cen = torch.randn(k, d, generator=g, device="cuda") * 3.0
+    true = torch.randint(0, k, (n,), generator=g, device="cuda")
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # blobs in chunks: no n x d f32 temporary
+        t = true[s0:s0 + step]
+        x[s0:s0 + step] = (cen[t] + torch.randn(len(t), d, generator=g, device="cuda")).to(torch.bfloat16)
+    xd = to_device_matrix(x.to(dt) if dt != torch.bfloat16 else x, d)
+    del x
+    rnd = torch.randint(0, k, (n,), generator=g, device="cuda")
+    lab = torch.where(torch.rand(n, generator=g, device="cuda") < 0.9, true, rnd).to(torch.int32)
+    del true, rnd
+    gb = xd.numel() * xd.element_size() / 1e9
+    for measure in (("squaredEuclidean", "cosine") if a.measure == "both" else (a.measure,)):
+        cos = measure == "cosine"
+        stats, _ = SO.cluster_stats_device(xd, lab, k, None, cos)
+        ts = best_ms(lambda: SO.cluster_stats_device(xd, lab, k, None, cos))
+        tw = best_ms(lambda: SO.label_wsum(xd, lab, k, None))
+        tn = best_ms(lambda: SO.row_sqnorm(xd))
+        tsc = best_ms(lambda: SO.silhouette_score(xd, lab, stats, None, cos))
+        part = SO.silhouette_score(xd, lab, stats, None, cos)
+        flop = 6.0 * n * max(32, xd.shape[1]) * 16 * (-(-k // 16))  # three bf16 MFMA terms per product
+        print(f"silhouette {n}x{d} {a.dtype} k={k} {measure}: stats pass {ts:.3f} ms (label_wsum with its sort "
+              f"{tw:.3f} ms, row norms {tn:.3f} ms); score pass {tsc:.3f} ms, {gb / tsc:.2f} TB/s rows, "
+              f"{flop / tsc / 1e9:.1f} TFLOP/s bf16 MFMA; silhouette {float(part[0] / part[1]):.6f}", flush=True)
+    if a.evaluate:
+        from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.evaluation import ClusteringEvaluator
+        from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+        spark = SparkSession.builder.master("mi355x").getOrCreate()
+        df = spark.createDataFrameFromTensors({"features": xd, "prediction": lab})
+        for measure in (("squaredEuclidean", "cosine") if a.measure == "both" else (a.measure,)):
+            ev = ClusteringEvaluator(distanceMeasure=measure)
+            ev.evaluate(df)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            v = ev.evaluate(df)
+            torch.cuda.synchronize()
+            print(f"evaluate {n}x{d} {a.dtype} k={k} {measure}: {(time.perf_counter() - t0) * 1e3:.1f} ms end to end, "
+                  f"silhouette {v:.6f}", flush=True)
+
+
+COMMANDS = {"silhouette": cmd_silhouette, "multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
