@@ -60,6 +60,7 @@ struct AssignShape {
   static constexpr int NCH = DP / 8;                 // 16-byte chunks per row
   static constexpr int KS = DP >= 32 ? DP / 32 : 1;  // MFMA k-steps per 16x16 block
 };
+constexpr int kAssignThreads = 512;
 
 // X fragments of one 16-row sub-tile: lane (row l&15, group g=l>>4) reads chunk 4s+g of its row,
 // so each load instruction covers 16 rows x 64 contiguous bytes.
@@ -156,31 +157,10 @@ __device__ __forceinline__ void slot_update(const f32x4 (&acc)[RT], int t, int i
   key[t][i] = k < key[t][i] ? k : key[t][i];
 }
 
-// PACK4: the 4 slots of sub-tile t hold the SAME X row against centres 4g+i, so they merge into
-// ONE key per row whose low bits carry (tile, i): 4 v_and_or + 2 v_min3_i32 per 4 distances
-// instead of 4 + 4 (and 4x fewer key registers). Two more mantissa bits are truncated
-// (2^-17 relative for k = 256).
 template <int RT>
-__device__ __forceinline__ void group_update(const f32x4 (&acc)[RT], int t, int ct4, int cmask, int (&key)[RT][4]) {
-  const int k0 = (__float_as_int(acc[t][0]) & ~cmask) | ct4;
-  const int k1 = (__float_as_int(acc[t][1]) & ~cmask) | (ct4 + 1);
-  const int k2 = (__float_as_int(acc[t][2]) & ~cmask) | (ct4 + 2);
-  const int k3 = (__float_as_int(acc[t][3]) & ~cmask) | (ct4 + 3);
-  int m = key[t][0];
-  m = min(m, min(k0, k1));
-  m = min(m, min(k2, k3));
-  key[t][0] = m;
-}
-
-template <int RT, bool PACK4>
 __device__ __forceinline__ void tile_update_all(const f32x4 (&acc)[RT], int ct, int cmask, int (&key)[RT][4]) {
-  if constexpr (PACK4) {
 #pragma unroll
-    for (int t = 0; t < RT; ++t) group_update<RT>(acc, t, ct << 2, cmask, key);
-  } else {
-#pragma unroll
-    for (int q = 0; q < RT * 4; ++q) slot_update<RT>(acc, q >> 2, q & 3, ct, cmask, key);
-  }
+  for (int q = 0; q < RT * 4; ++q) slot_update<RT>(acc, q >> 2, q & 3, ct, cmask, key);
 }
 
 // MFMA chain of centre tile `ct` for all RT sub-tiles into `acc` (each A fragment feeds RT
@@ -193,22 +173,16 @@ __device__ __forceinline__ void tile_update_all(const f32x4 (&acc)[RT], int ct, 
 // Precision: a row's candidates carry the offset moff − ||x||², so their f32 rounding is on the
 // scale of the tile's largest norm instead of the row's own. That only matters for rows sharing
 // a 64-row tile with an outlier ~100x their norm; bf16 quantisation of x (2^-8 relative in x·c)
-// is the larger error below that.
-// SHARED = false keeps the per-sub-tile seeding (c4 + ||x||² of each row) — the A/B reference of
-// kmeans_ops.set_assign_variant(6); in one process it measured 2.77 vs 2.71 ms full and 2.15 vs
-// 2.07 ms compute-only (profiles/assign_shared_seed_ab_20Mx256.log).
-template <int DP, int RT, int RING, bool PREV, bool SHARED, bool PACK4>
-__device__ __forceinline__ void chain(const AssignCtx& cx, const XTile<DP, RT>& xt, float moff,
-                                      const float (&xn)[RT], int ct, int g, f32x4 (&acc)[RT],
+// is the larger error below that. (Per-sub-tile seeding measured 2.77 vs 2.71 ms full and 2.15 vs
+// 2.07 ms compute-only, profiles/assign_shared_seed_ab_20Mx256.log.)
+template <int DP, int RT, int RING, bool PREV>
+__device__ __forceinline__ void chain(const AssignCtx& cx, const XTile<DP, RT>& xt, float moff, int ct, int g,
+                                      f32x4 (&acc)[RT],
                                       const f32x4 (&prev)[RT], uint4 (&ring)[RING], int (&key)[RT][4]) {
   constexpr int KS = AssignShape<DP>::KS;
   constexpr int NSLOT = RT * 4;
   const float4 c4 = *reinterpret_cast<const float4*>(cx.cn + ct * 16 + 4 * g);
   const f32x4 cinit = {c4.x + moff, c4.y + moff, c4.z + moff, c4.w + moff};
-  if constexpr (!SHARED) {
-#pragma unroll
-    for (int t = 0; t < RT; ++t) acc[t] = f32x4{c4.x + xn[t], c4.y + xn[t], c4.z + xn[t], c4.w + xn[t]};
-  }
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     const uint4 a = ring[s % RING];
@@ -216,11 +190,8 @@ __device__ __forceinline__ void chain(const AssignCtx& cx, const XTile<DP, RT>& 
 #pragma unroll
     for (int t = 0; t < RT; ++t)
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), xt.f[t][s],
-                                                       (SHARED && s == 0) ? cinit : acc[t], 0, 0, 0);
-    if constexpr (PREV && PACK4) {
-#pragma unroll
-      for (int t = (s * RT) / KS; t < ((s + 1) * RT) / KS; ++t) group_update<RT>(prev, t, (ct - 1) << 2, cx.cmask, key);
-    } else if constexpr (PREV) {
+                                                       s == 0 ? cinit : acc[t], 0, 0, 0);
+    if constexpr (PREV) {
 #pragma unroll
       for (int q = (s * NSLOT) / KS; q < ((s + 1) * NSLOT) / KS; ++q)
         slot_update<RT>(prev, q >> 2, q & 3, ct - 1, cx.cmask, key);
@@ -242,7 +213,7 @@ struct DeltaOut {
   int* lds_count;  // set in the kernel
 };
 
-template <int DP, int RT, int RINGMAX, bool SHARED, bool PACK4>
+template <int DP, int RT, int RINGMAX>
 __device__ __forceinline__ void assign_tile(const AssignCtx& cx, const XTile<DP, RT>& xt, long long tile,
                                             long long n, int r, int g, int c_base, const float* __restrict__ xnorm,
                                             int* __restrict__ labels, float* __restrict__ best_io, int first,
@@ -268,34 +239,28 @@ __device__ __forceinline__ void assign_tile(const AssignCtx& cx, const XTile<DP,
   for (int q = 0; q < RING; ++q) ring[q] = frag_at<DP>(cx, q / KS, q % KS);
   f32x4 acc0[RT], acc1[RT];
   const int nct = cx.nct;
-  chain<DP, RT, RING, false, SHARED, PACK4>(cx, xt, moff, xn, 0, g, acc0, acc1, ring, key);
+  chain<DP, RT, RING, false>(cx, xt, moff, 0, g, acc0, acc1, ring, key);
   int ct = 1;
   for (; ct + 1 < nct; ct += 2) {
-    chain<DP, RT, RING, true, SHARED, PACK4>(cx, xt, moff, xn, ct, g, acc1, acc0, ring, key);
-    chain<DP, RT, RING, true, SHARED, PACK4>(cx, xt, moff, xn, ct + 1, g, acc0, acc1, ring, key);
+    chain<DP, RT, RING, true>(cx, xt, moff, ct, g, acc1, acc0, ring, key);
+    chain<DP, RT, RING, true>(cx, xt, moff, ct + 1, g, acc0, acc1, ring, key);
   }
   if (ct < nct) {
-    chain<DP, RT, RING, true, SHARED, PACK4>(cx, xt, moff, xn, ct, g, acc1, acc0, ring, key);
-    tile_update_all<RT, PACK4>(acc1, ct, cx.cmask, key);
+    chain<DP, RT, RING, true>(cx, xt, moff, ct, g, acc1, acc0, ring, key);
+    tile_update_all<RT>(acc1, ct, cx.cmask, key);
   } else {
-    tile_update_all<RT, PACK4>(acc0, ct - 1, cx.cmask, key);
+    tile_update_all<RT>(acc0, ct - 1, cx.cmask, key);
   }
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
     // slot (t,i) holding tile c is centre 16c + 4g + i
     float best = __int_as_float(key[t][0] & ~cx.cmask);
-    int bidx;
-    if constexpr (PACK4) {
-      const int tag = key[t][0] & cx.cmask;  // (tile << 2) | i: centre 16 tile + 4g + i
-      bidx = (tag >> 2) * 16 + 4 * g + (tag & 3);
-    } else {
-      bidx = (key[t][0] & cx.cmask) * 16 + 4 * g;
+    int bidx = (key[t][0] & cx.cmask) * 16 + 4 * g;
 #pragma unroll
-      for (int i = 1; i < 4; ++i) {
-        const float v = __int_as_float(key[t][i] & ~cx.cmask);
-        const int idx = (key[t][i] & cx.cmask) * 16 + 4 * g + i;
-        if (v < best || (v == best && idx < bidx)) { best = v; bidx = idx; }
-      }
+    for (int i = 1; i < 4; ++i) {
+      const float v = __int_as_float(key[t][i] & ~cx.cmask);
+      const int idx = (key[t][i] & cx.cmask) * 16 + 4 * g + i;
+      if (v < best || (v == best && idx < bidx)) { best = v; bidx = idx; }
     }
 #pragma unroll
     for (int o = 16; o <= 32; o <<= 1) {
@@ -304,7 +269,7 @@ __device__ __forceinline__ void assign_tile(const AssignCtx& cx, const XTile<DP,
       if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
     }
     bidx += c_base;
-    if constexpr (SHARED) best = best - moff + xn[t];  // remove the row offset: squared distance
+    best = best - moff + xn[t];  // remove the row offset: squared distance
     const long long row = tile * (16 * RT) + 16 * t + r;
     const bool mine = g == 0 && row < n;
     if (!first && mine) {
@@ -344,17 +309,18 @@ __device__ __forceinline__ void assign_tile(const AssignCtx& cx, const XTile<DP,
   }
 }
 
-// NT threads; each wave owns super-tiles of RT x 16 rows. PF: the next super-tile's rows are in
-// flight while this one computes (double-buffered X registers).
-template <int DP, int RT, int NT, bool PF, int RINGMAX, bool F8, bool SHARED = true, bool PACK4 = false>
-__global__ __launch_bounds__(NT, 1) void kmeans_assign_bf16(
+// kAssignThreads threads; each wave owns super-tiles of RT x 16 rows. PF: the next super-tile's rows
+// are in flight while this one computes (double-buffered X registers). RINGMAX: centre fragments in flight.
+template <int DP, int RT, bool PF, int RINGMAX, bool F8>
+__global__ __launch_bounds__(kAssignThreads, 1) void kmeans_assign_bf16(
     const void* __restrict__ X, long long n, long long ldx, const u16* __restrict__ C, long long ldc,
     int kc, int kp, int c_base, const float* __restrict__ cnorm, const float* __restrict__ xnorm,
     int* __restrict__ labels, float* __restrict__ best_io, int first, int last, double* __restrict__ cost_part,
-    int* __restrict__ hist_out, int* __restrict__ rank_out, DeltaOut dout, int sched) {
+    int* __restrict__ hist_out, int* __restrict__ rank_out, DeltaOut dout) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NCH = AssignShape<DP>::NCH;
   constexpr int KS = AssignShape<DP>::KS;
+  constexpr int NT = kAssignThreads;
   const int nct = kc >> 4;
   uint4* fr = reinterpret_cast<uint4*>(smem);
   float* cn = reinterpret_cast<float*>(smem + (size_t)nct * KS * 1024);
@@ -401,37 +367,28 @@ __global__ __launch_bounds__(NT, 1) void kmeans_assign_bf16(
   cx.nct = nct;
   int bits = 1;
   while ((1 << bits) < nct) ++bits;
-  if (PACK4) bits += 2;
   cx.cmask = (1 << bits) - 1;
 
   long long tile = (long long)blockIdx.x * nwaves + wave;
-  // SIMD partners (waves w and w + 4) run the same program: desynchronise them so one streams its
-  // next X tile while the other computes (sched bit 0: static priority for the second half, bit 1:
-  // the second half starts ~sched>>2 x 512 cycles late).
-  if (wave >= nwaves / 2) {
-    if (sched & 1) __builtin_amdgcn_s_setprio(1);
-    if (sched & 2)
-      for (int i = 0; i < (sched >> 2); ++i) __builtin_amdgcn_s_sleep(8);
-  }
   if constexpr (PF) {
     XTile<DP, RT> xa, xb;
     if (tile < ntiles) load_xtile<DP, RT, F8>(X, n, ldx, tile, r, g, xa);
     for (; tile < ntiles; tile += 2 * tw) {
       const long long t1 = tile + tw;
       if (t1 < ntiles) load_xtile<DP, RT, F8>(X, n, ldx, t1, r, g, xb);
-      assign_tile<DP, RT, RINGMAX, SHARED, PACK4>(cx, xa, tile, n, r, g, c_base, xnorm, labels, best_io, first, last, ranking, hist,
-                          rank_out, dout, cost);
+      assign_tile<DP, RT, RINGMAX>(cx, xa, tile, n, r, g, c_base, xnorm, labels, best_io, first, last, ranking, hist, rank_out, dout,
+                      cost);
       if (t1 >= ntiles) break;
       if (t1 + tw < ntiles) load_xtile<DP, RT, F8>(X, n, ldx, t1 + tw, r, g, xa);
-      assign_tile<DP, RT, RINGMAX, SHARED, PACK4>(cx, xb, t1, n, r, g, c_base, xnorm, labels, best_io, first, last, ranking, hist,
-                          rank_out, dout, cost);
+      assign_tile<DP, RT, RINGMAX>(cx, xb, t1, n, r, g, c_base, xnorm, labels, best_io, first, last, ranking, hist, rank_out, dout,
+                      cost);
     }
   } else {
     for (; tile < ntiles; tile += tw) {
       XTile<DP, RT> xt;
       load_xtile<DP, RT, F8>(X, n, ldx, tile, r, g, xt);
-      assign_tile<DP, RT, RINGMAX, SHARED, PACK4>(cx, xt, tile, n, r, g, c_base, xnorm, labels, best_io, first, last, ranking, hist,
-                          rank_out, dout, cost);
+      assign_tile<DP, RT, RINGMAX>(cx, xt, tile, n, r, g, c_base, xnorm, labels, best_io, first, last, ranking, hist, rank_out, dout,
+                      cost);
     }
   }
   if (last && (cost_part != nullptr || ranking)) {
@@ -1528,42 +1485,27 @@ long long assign_lds_bytes(int kc, int kp, int Dp) {
 // per byte: RT 4 halves the LDS fragment traffic and amortises the per-tile epilogue (no X
 // double buffer fits next to it; the partner wave hides the loads). Small rows are bytes-heavy:
 // RT 1 with the next tile's X in flight and more waves per CU.
-// Variant (tuning/experiments): 0 auto, 1 = RT 2 + X double buffer, 2 = RT 1, 3 = RT 4.
+// Variant: 0 auto, 1 = RT 2 + X double buffer, 2 = RT 1, 3 = RT 4 (the launch shapes the Lloyd-step
+// test runs against the reference), 8 forces K9r.
 int g_assign_variant = 0;
-int g_assign_sched = 0;
 // K9r (kmeans_rr.h, register-resident centres + LDS-DMA X ring) on variant 8, and by default
 // (variant 0) wherever rr::plan_ct accepts the shape while this is set (CML_KMEANS_RR=0 turns it off).
 // Measured (profiles/r2_assign_rr.md): 100M x 256, k = 256: 12.2 vs 13.2 ms; 10M x 128, k = 64: 0.457 vs
 // 0.509 ms.
 int g_rr_default = 1;
-int g_rr_dbg = 0;  // K9r ablation bits (kmeans_rr.h), 0 in production  // kmeans_assign_bf16 `sched` (partner-wave desynchronisation), tuning knob
-inline int assign_threads(int /*DS*/) {
-  return g_assign_variant == 4 ? 768 : (g_assign_variant == 5 ? 1024 : 512);
-}
+int g_rr_dbg = 0;  // K9r ablation bits (kmeans_rr.h), 0 in production
 
 template <int DP, bool F8>
 const void* assign_kernel_ptr() {
   constexpr bool PF = AssignShape<DP>::KS <= 8;
   constexpr int RT_BIG = DP >= 512 ? 2 : 4;
   switch (g_assign_variant) {
-    case 1: return (const void*)kmeans_assign_bf16<DP, 2, 512, PF, 4, F8>;
-    case 2: return (const void*)kmeans_assign_bf16<DP, 1, 512, PF, 4, F8>;
-    case 3: return (const void*)kmeans_assign_bf16<DP, RT_BIG, 512, false, 2, F8>;
-    case 4: return (const void*)kmeans_assign_bf16<DP, 2, 768, false, 4, F8>;
-    case 5: return (const void*)kmeans_assign_bf16<DP, 1, 1024, PF, 4, F8>;
-    case 6:  // the default launch with per-sub-tile accumulator seeding (A/B reference of SHARED)
-      if constexpr (DP >= 256)
-        return (const void*)kmeans_assign_bf16<DP, RT_BIG, 512, false, DP >= 512 ? 4 : 2, F8, false>;
-      else
-        return (const void*)kmeans_assign_bf16<DP, 1, 512, PF, 4, F8, false>;
-    case 7:  // the default launch with the PACK4 per-row key (4 slots merged by v_min3)
-      if constexpr (DP >= 256)
-        return (const void*)kmeans_assign_bf16<DP, RT_BIG, 512, false, DP >= 512 ? 4 : 2, F8, true, true>;
-      else
-        return (const void*)kmeans_assign_bf16<DP, 1, 512, PF, 4, F8, true, true>;
+    case 1: return (const void*)kmeans_assign_bf16<DP, 2, PF, 4, F8>;
+    case 2: return (const void*)kmeans_assign_bf16<DP, 1, PF, 4, F8>;
+    case 3: return (const void*)kmeans_assign_bf16<DP, RT_BIG, false, 2, F8>;
     default:
-      if constexpr (DP >= 256) return (const void*)kmeans_assign_bf16<DP, RT_BIG, 512, false, DP >= 512 ? 4 : 2, F8>;
-      else return (const void*)kmeans_assign_bf16<DP, 1, 512, PF, 4, F8>;
+      if constexpr (DP >= 256) return (const void*)kmeans_assign_bf16<DP, RT_BIG, false, DP >= 512 ? 4 : 2, F8>;
+      else return (const void*)kmeans_assign_bf16<DP, 1, PF, 4, F8>;
   }
 }
 
@@ -1574,10 +1516,6 @@ inline int assign_tile_rows(int Dp) {
     case 1: return 32;
     case 2: return 16;
     case 3: return Dp >= 512 ? 32 : 64;
-    case 4: return 32;
-    case 5: return 16;
-    case 6: return Dp >= 512 ? 32 : (Dp >= 256 ? 64 : 16);
-    case 7: return Dp >= 512 ? 32 : (Dp >= 256 ? 64 : 16);
     default: return Dp >= 512 ? 32 : (Dp >= 256 ? 64 : 16);
   }
 }
@@ -1588,7 +1526,7 @@ int assign_occupancy(int kc, int kp) {
   const void* fn = assign_kernel_ptr<DP, F8>();
   hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int nb = 0;
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, assign_threads(0), lds);
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kAssignThreads, lds);
   return nb;
 }
 
@@ -1601,9 +1539,8 @@ int launch_assign(const void* X, long long n, long long ldx, const u16* C, long 
   hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   void* args[] = {(void*)&X, (void*)&n, (void*)&ldx, (void*)&C, (void*)&ldc, (void*)&kc, (void*)&kp,
                   (void*)&c_base, (void*)&cnorm, (void*)&xnorm, (void*)&labels, (void*)&best, (void*)&first,
-                  (void*)&last, (void*)&cost_part, (void*)&hist, (void*)&rank, (void*)&dout,
-                  (void*)&g_assign_sched};
-  const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(assign_threads(0)), args, lds, st);
+                  (void*)&last, (void*)&cost_part, (void*)&hist, (void*)&rank, (void*)&dout};
+  const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kAssignThreads), args, lds, st);
   if (e != hipSuccess) return (int)e;
   return cml_status();
 }
@@ -1661,7 +1598,7 @@ int launch_segsum(const void* X, long long n, long long ldx, int Dp, int D, cons
 }  // namespace
 
 CML_API long long cml_kmeans_assign_lds_bytes(int kc, int kp, int Dp) { return assign_lds_bytes(kc, kp, Dp); }
-CML_API int cml_kmeans_assign_threads(int Dp) { return assign_threads(Dp / 16); }
+CML_API int cml_kmeans_assign_threads(int /*Dp*/) { return kAssignThreads; }
 // Resident workgroups per CU of the assign kernel for this shape (persistent-grid sizing).
 CML_API int cml_kmeans_assign_occupancy(int Dp, int kc, int kp, int xfp8) {
   if (xfp8) {
@@ -1682,11 +1619,6 @@ CML_API int cml_kmeans_assign_occupancy(int Dp, int kc, int kp, int xfp8) {
     case 32: return assign_occupancy<512, false>(kc, kp);
     default: return 0;
   }
-}
-CML_API int cml_kmeans_set_assign_sched(int v) {
-  if (v < 0) return (int)hipErrorInvalidValue;
-  g_assign_sched = v;
-  return 0;
 }
 // K9r plan for (Dp, kc): returns the centre tiles per compute wave (0: K9r not used — variant, fp8 rows
 // or shape), out[0] = LDS bytes, out[1] = rows per tile (= rows per workgroup round), out[2] = threads.
@@ -1723,7 +1655,7 @@ CML_API int cml_kmeans_set_rr_default(int on) {
 // Rows per wave tile of the K9 launch the current variant selects (sort-regime scatter geometry).
 CML_API int cml_kmeans_assign_tile_rows(int Dp) { return assign_tile_rows(Dp); }
 CML_API int cml_kmeans_set_assign_variant(int v) {
-  if (v < 0 || v > 8) return (int)hipErrorInvalidValue;
+  if (v != 8 && (v < 0 || v > 3)) return (int)hipErrorInvalidValue;
   g_assign_variant = v;
   return 0;
 }
@@ -1918,13 +1850,6 @@ CML_API int cml_kmeans_delta_gate(const int* chg_wg_count, int nblk, int cap, in
   return cml_status();
 }
 
-int g_delta_fused_fixup = 1;  // cml_kmeans_set_delta_fused_fixup (A/B knob)
-CML_API int cml_kmeans_set_delta_fused_fixup(int on) {
-  const int prev = g_delta_fused_fixup;
-  if (on >= 0) g_delta_fused_fixup = on;
-  return prev;
-}
-
 // dseg: 2k+1 ints, cursor: 2k ints, dperm: 2*cap ints, dsum: 2k*D doubles; slots/slot_c sized for
 // seg_grid (cml_kmeans_seg_slot_*); acc/msg: k*D + k + 1 doubles.
 CML_API int cml_kmeans_delta_accum(const void* X, long long ldx, int Dp, int D, const int* labels, const int* chg_rows,
@@ -1942,17 +1867,16 @@ CML_API int cml_kmeans_delta_accum(const void* X, long long ldx, int Dp, int D, 
   int e = cml_status();
   if (e) return e;
   // the cross-slice partials: added by the apply (per element, seg_fix) instead of a fixup launch (one
-  // workgroup per key); CML_DELTA_FUSED_FIXUP=0 keeps the launch (A/B: profiles/r5/README.md)
-  const bool fused = g_delta_fused_fixup != 0;
+  // workgroup per key; the launch measured 93.7-93.8 against 93.5-93.6 ms, profiles/r5/ab_fixup/summary.txt)
   if (cap > 0) {
     e = launch_segsum(X, 2LL * cap, ldx, Dp, D, dperm, dseg, 2 * k, cpl, seg_grid, dsum, slots, slot_c, xfp8, mode, 0,
-                      st, SegUB{nullptr, 0, nullptr, qscale}, !fused);
+                      st, SegUB{nullptr, 0, nullptr, qscale}, /*fixup=*/false);
     if (e) return e;
   }
   const long long total = (long long)k * D + k + 1;
   const long long waves = (long long)seg_grid * (kSegThreads / 64);
   hipLaunchKernelGGL(kmeans_delta_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, acc, dsum, dseg,
-                     mode, k, D, cost_part, ncost, msg, (cap > 0 && fused) ? slots : nullptr, slot_c, 2LL * cap, waves);
+                     mode, k, D, cost_part, ncost, msg, cap > 0 ? slots : nullptr, slot_c, 2LL * cap, waves);
   return cml_status();
 }
 

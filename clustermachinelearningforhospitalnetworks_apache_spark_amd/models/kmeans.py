@@ -268,7 +268,6 @@ class LloydEngine:
         self.prune = bool(prune)
         self.track_prune = False  # record (full?, re-assigned rows) of every pruned step (host reads)
         self._pdev = False  # the device pruned step (_step_prune_dev) is in use, decided in _alloc_gpu
-        self._seed_ub = os.environ.get("CML_KMEANS_SEED_UB", "1") != "0"  # A/B knob: exact ubs from the seeded sums
         if self.prune:  # one row chunk; the device form keeps incremental sums, the torch form its own
             row_chunks = 1
         # spherical = Spark's distanceMeasure="cosine": rows are scaled to unit length once, centres
@@ -298,6 +297,7 @@ class LloydEngine:
         self.gpu = (x.is_cuda or streamed) and precision == "bf16"
         self.n = int(x.shape[0])
         self.device = torch.device(device) if streamed else x.device
+        self._scr = None  # screen state (precision "screen"), see _screen_state
         if streamed:
             from ..utils.hoststream import HostRowStream, cached_stream
             self.x = x
@@ -318,7 +318,6 @@ class LloydEngine:
             self.x = x if (x.shape[1] == d and x.is_contiguous()) else (
                 x[:, :d] if x[:, :d].is_contiguous() else x[:, :d].contiguous())
             self.dp = d
-            self._scr = None
         else:
             self.x = x[:, :d].to(torch.float64)
             self.dp = d
@@ -355,6 +354,20 @@ class LloydEngine:
         # sum grid of the device sort-regime accumulates (_sum_grid): qscale 0 / unit 1 = plain f64 sums
         self._qscale, self._unit, self._grid_done = 0.0, 1.0, False
         self.sum_grid = None  # the grid step when the rows are summed on a grid
+        # lazily filled state, declared here so every later read is a plain attribute read
+        self.labels = None  # per-row labels: _alloc_gpu, or the first host / exact step
+        self._gn = None  # global row count (global_n)
+        self._gxmax = None  # max ||x||² over every rank (_xmax_dev)
+        self._seed = None  # labels / costs of this engine's k-means|| init (seeds the first step's bounds)
+        self._seeded = False  # the next step is _step_seeded
+        self._consumed = False  # the fit's final assignment took over the step state
+        self._er_event = None  # exponent range prefetched behind the row pass (_prefetch_erange)
+        self._graph_warm = False
+        self._scr_scratch = None
+        self._shift_pair = None
+        self._iscr = None  # scratch of the k-means|| candidate passes (_init_scratch)
+        self._rr_max = None  # _rr_max_chunk
+        self._init_prune_history = []  # (rows, per-row path, K9r pass) of the pruned k-means|| rounds (track_prune)
         if self.gpu:
             self._alloc_gpu()
 
@@ -498,7 +511,7 @@ class LloydEngine:
 
     @property
     def global_n(self) -> int:
-        if getattr(self, "_gn", None) is None:
+        if self._gn is None:
             self._gn = int(self.comm.sum_scalar(float(self.n)))
         return self._gn
 
@@ -526,10 +539,10 @@ class LloydEngine:
         if self.gpu:
             K.update_centers(None, self.k, self.d, self.centers, self.cb, self.dp, self.kp, self.cnorm, None,
                              snap=self._mx)
-        if getattr(self, "_scr", None) is not None and getattr(self._scr, "cert", None) is not None:
+        if self._scr is not None and getattr(self._scr, "cert", None) is not None:
             self._scr.cert.valid = False  # the certified step restarts from a screened full assignment
         self._shift_pair = None
-        seed, self._seed = getattr(self, "_seed", None), None
+        seed, self._seed = self._seed, None
         if self._pdev:  # bounds and incremental sums were relative to the old centres: a full step next
             st = self._pst
             K.centre_stats(self.cb, None, self.k, self.d, st.mx, st.tau, st.cn, st.half, st.drift, st.thr, st.dmax,
@@ -552,7 +565,7 @@ class LloydEngine:
     # ------------------------------------------------------------------ iteration
     def step(self) -> None:
         """One Lloyd iteration over the global dataset (all ranks participate)."""
-        if getattr(self, "_consumed", False):
+        if self._consumed:
             raise RuntimeError("LloydEngine: the fit's final assignment consumed this engine's step state")
         self._ensure_norms()
         self._sum_grid()
@@ -562,7 +575,7 @@ class LloydEngine:
             if self._pdev:  # a pruned step has no counting-sort ranks of every row: a full step
                 self._pst.force.fill_(1)
         if self._pdev:
-            if getattr(self, "_seeded", False):
+            if self._seeded:
                 self._seeded = False
                 self._step_seeded()
             elif self.use_graph:
@@ -604,7 +617,7 @@ class LloydEngine:
                 for _, r0, r1, xc in self._x_chunks(whole=True):
                     K.row_pass(xc, r1 - r0, self.dp, tmp[r0:r1], erange=er)
             self._erange = er
-        if getattr(self, "_er_event", None) is not None:  # prefetched behind the row pass (_prefetch_erange)
+        if self._er_event is not None:  # prefetched behind the row pass (_prefetch_erange)
             self._er_event.synchronize()
             lo, hi = int(self._er_host[0]), int(self._er_host[1])
             self._er_event = None
@@ -630,7 +643,7 @@ class LloydEngine:
         graph reads in place: new centres from set_centers/update are picked up by the replay."""
         split = self._pdev and self.comm.is_distributed  # graph | all-reduce | graph
         if self._graph is None:
-            if not getattr(self, "_graph_warm", False):
+            if not self._graph_warm:
                 self._graph_warm = True
                 (self._step_prune_dev if self._pdev else self._step_gpu)()
                 return
@@ -842,7 +855,7 @@ class LloydEngine:
         return lab[:n].long(), (best[:n].clone() if want_dist else None)
 
     def _scr_best(self) -> torch.Tensor:
-        if getattr(self, "_scr_scratch", None) is None:
+        if self._scr_scratch is None:
             self._scr_scratch = torch.empty(max(self.n, 1), dtype=torch.float64, device=self.device)
         return self._scr_scratch
 
@@ -1057,7 +1070,7 @@ class LloydEngine:
         pad = round_up(st.cap_m, tr) + tr
         # the candidate lists and the small per-step state: views of one zeroed block (one fill instead of
         # sixteen). pmode = [full pass?, re-assigned rows]; mx = max ||x||² over all ranks (_ensure_norms)
-        lazy = os.environ.get("CML_KMEANS_LAZY_BOUNDS", "1") != "0" and k <= 4096
+        lazy = k <= 4096
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
         (st.cand, st.cand_lab, st.cand_xn, st.count, st.pmode, st.backoff, st.drift, st.thr, st.dmax, st.cn, st.half,
          st.mc, st.c2, st.mx, cum, st.ctr) = K.zeros_block(dev, [
@@ -1076,11 +1089,10 @@ class LloydEngine:
         st.cb_cost = torch.zeros_like(self.cb)  # centres of the last live step's assignment (training cost)
         # offset-form bounds (kmeans_prune.hip bound_lazy): ub/lb hold ub - cu[label] / lb + cl[label]
         # against these cumulative drifts [cu | cl], so the bounds pass only reads the rows whose label
-        # holds; CML_KMEANS_LAZY_BOUNDS=0 keeps the absolute bounds rewritten every step
+        # holds; k > 4096 keeps the absolute bounds rewritten every step
         st.cum = cum if lazy else None
         # completion counters of the fused launches (gate in the bounds pass, stats in the half pass); each
-        # launch leaves its counter at zero. CML_KMEANS_FUSED_TAIL=0: the separate launches (A/B)
-        st.fused = os.environ.get("CML_KMEANS_FUSED_TAIL", "1") != "0"
+        # launch leaves its counter at zero (st.ctr)
         st.half_every = int(os.environ.get("CML_KMEANS_HALF_EVERY", "4"))
         # recorded launch sequences of the step variants (_pdev_pre / _pdev_post); None: always the wrappers
         st.replay = {} if os.environ.get("CML_KMEANS_REPLAY", "1") != "0" else None
@@ -1109,87 +1121,22 @@ class LloydEngine:
         writing new labels and top-2 bounds and logging label changes; the incremental sums move by
         the changed rows (exact f64 sums, as the full path); all-reduce; K11; centre statistics for
         the next step's bounds."""
-        if not self._pdev_pre():
-            self.comm.allreduce_async(self.msgs[0]).wait()
+        self._pdev_pre()
+        self.comm.allreduce_async(self.msgs[0]).wait()
         self._pdev_post()
 
-    def _pdev_pre(self) -> bool:
-        """The device pruned step up to its all-reduce (bounds, gate, K9r passes, sums -> msg). True when the
-        step ran split (_pdev_pre_split), which all-reduces its own two messages into msgs[0]."""
+    def _pdev_pre(self) -> None:
+        """The device pruned step up to its all-reduce (bounds, gate, K9r passes, sums -> msg)."""
         st, dl = self._pst, self.delta
-        hint_full = st.fused and int(st.pm_host[0]) != 0
-        if hint_full and dl.lean_step() and not torch.cuda.is_current_stream_capturing():
-            split = self._full_split(self.n)
-            if split is not None:
-                self._pdev_pre_split(split)
-                return True
+        hint_full = int(st.pm_host[0]) != 0
         lean = dl.lean_step() and not hint_full
         if self._replay_ok():
             # the launch sequence of this variant, recorded once (fixed buffers and scalars): replayed without
             # the Python wrappers — the shard's steps were bound by ~25 us of host time per launch
             if self._replay(("pre", lean), lambda: self._pdev_pre_launches(lean)):
                 dl.host_forced = False  # what the recorded gate does on the host
-                return False
+                return
         self._pdev_pre_launches(lean)
-        return False
-
-    def _full_split(self, n: int):
-        """Row halves of a full-pass step whose first half's all-reduce overlaps the second half's K9r pass
-        (_pdev_pre_split), or None. Opt-in (CML_KMEANS_SPLIT_FULL=1, on any rank count, with at
-        least CML_KMEANS_OVERLAP_ROWS local rows): the Lloyd message is [k·D | k | 1] whatever the chunk, so the
-        second chunk's all-reduce is as long as the unsplit one and stays exposed — the split hides nothing of a
-        latency-bound 257 KiB all-reduce and pays a second delta-sums pipeline and K9r ramp (measured with a
-        one-rank RCCL group at the 8-GPU shard, 12.5M overlap-data rows: 2.25 vs 2.07 ms per step;
-        profiles/r6/README.md). It is kept, tested bit for bit, for bandwidth-bound messages (very large k·D)."""
-        force = os.environ.get("CML_KMEANS_SPLIT_FULL")
-        if force != "1":
-            return None
-        lim = int(os.environ.get("CML_KMEANS_OVERLAP_ROWS", 4_000_000))  # (the split is opt-in above)
-        if lim <= 0 or n < max(lim, 2 * self.aplan.round_rows):
-            return None
-        mid = min(n - 1, max(1, round_up(n // 2, 1024)))
-        return mid
-
-    def _pdev_pre_split(self, mid: int) -> None:
-        """A full-pass pruned step in two row chunks, its all-reduce overlapped with the distance GEMM (the north
-        star's "all-reduce overlapped with the next shard's distance GEMM"): the bounds pass and gate over every
-        row; chunk 0 = the K9r mode-1 pass over rows [0, mid) (or, when the gate picked candidates, the candidate
-        pass over every candidate) and its delta sums -> message A, whose all-reduce is enqueued at once; chunk 1
-        = the mode-1 pass over rows [mid, n) and its delta sums -> B = the sums' change since A; msgs[0] = A + B.
-        The sums are exact (_sum_grid), so A + B is the one-message step bit for bit on any rank count. Lean
-        (delta) sums only: taken when the host's lagged hint says the gate is picking full passes."""
-        st, dl, ap = self._pst, self.delta, self.aplan
-        n, k, dp = self.n, self.k, self.dp
-        x, lab, xn = self.x, self.labels, self.xnorm
-        if getattr(self, "_msgs_split", None) is None:
-            self._msgs_split = torch.zeros((3, self.msg_len), dtype=torch.float64, device=self.device)
-        A, B, loc = self._msgs_split[0], self._msgs_split[1], self._msgs_split[2]
-        K.prune_bounds_gated(lab[:n], st.ub, st.lb, st.drift, st.dmax, st.thr, st.c2, k, st.cand, st.count, xn,
-                             st.cand_lab, st.cand_xn, st.flags, st.cum, st.pmode, st.cap_m,
-                             st.backoff if st.nback > 0 else None, st.nback, st.ctr[0:1], mode_host=st.pm_host)
-        K.assign_rr_ext(1, x[:mid], mid, dp, self.cb, self.cnorm, ap, xn[:mid], lab[:mid], self.cost_part, st.ub[:mid],
-                        st.lb[:mid], st.mc, st.tau, delta=dl, gate=st.pmode, want=1, cum=st.cum)
-        K.assign_rr_ext(2, x, st.cap_m, dp, self.cb, self.cnorm, ap, st.cand_xn, lab, self.cost_part, st.ub, st.lb,
-                        st.mc, st.tau, delta=dl, idx=st.cand, n_dev=st.count, lab_in=st.cand_lab, gate=st.pmode,
-                        want=0, cum=st.cum)
-        dl.gate(0, lean=True)
-        dl.accumulate(x, dp, lab, 0, self.cost_part, ap.grid, A, qscale=self._qscale)
-        loc.copy_(A)  # this rank's sums after chunk 0 (A is all-reduced in place)
-        h0 = self.comm.allreduce_async(A)
-        # chunk 1 — its K9r pass runs while A's all-reduce is in flight. (Its change lists start empty: a gated-off
-        # pass, when the gate picked candidates, leaves chunk 0's counts behind.)
-        dl.wg_count.zero_()
-        r = n - mid
-        K.assign_rr_ext(1, x[mid:], r, dp, self.cb, self.cnorm, ap, xn[mid:n], lab[mid:n], self.cost_part,
-                        st.ub[mid:n], st.lb[mid:n], st.mc, st.tau, delta=dl, gate=st.pmode, want=1, cum=st.cum)
-        dl.gate(0, lean=True)
-        dl.accumulate(x[mid:], dp, lab[mid:n], 0, self.cost_part, ap.grid, B, qscale=self._qscale)
-        B.sub_(loc)  # the change of this rank's sums over chunk 1 (exact: grid sums)
-        h1 = self.comm.allreduce_async(B)
-        h0.wait()
-        h1.wait()
-        torch.add(A, B, out=self.msgs[0])
-        st.split_steps = getattr(st, "split_steps", 0) + 1
 
     def _replay(self, key, launches) -> bool:
         """Replay the recorded launch sequence ``key`` of the current stream, recording it first (or again,
@@ -1218,16 +1165,10 @@ class LloydEngine:
         st, dl = self._pst, self.delta
         n, k, d, ap = self.n, self.k, self.d, self.aplan
         x, lab, msg = self.x, self.labels, self.msgs[0]
-        if st.fused:  # bounds pass + gate in one launch
-            K.prune_bounds_gated(lab[:n], st.ub, st.lb, st.drift, st.dmax, st.thr, st.c2, k, st.cand, st.count,
-                                 self.xnorm, st.cand_lab, st.cand_xn, st.flags, st.cum, st.pmode, st.cap_m,
-                                 st.backoff if st.nback > 0 else None, st.nback, st.ctr[0:1], mode_host=st.pm_host)
-        else:
-            K.prune_bounds(lab, st.ub, st.lb, st.drift, st.dmax, st.thr, st.c2, k, st.cand, st.count,
-                           xn=self.xnorm, cand_lab=st.cand_lab, cand_xn=st.cand_xn, skip=st.flags, zero_count=False,
-                           cum=st.cum) if n else None
-            K.prune_gate(st.count, st.cap_m, st.flags, st.pmode, backoff=st.backoff if st.nback > 0 else None,
-                         nback=st.nback)
+        # bounds pass + gate in one launch
+        K.prune_bounds_gated(lab[:n], st.ub, st.lb, st.drift, st.dmax, st.thr, st.c2, k, st.cand, st.count,
+                             self.xnorm, st.cand_lab, st.cand_xn, st.flags, st.cum, st.pmode, st.cap_m,
+                             st.backoff if st.nback > 0 else None, st.nback, st.ctr[0:1], mode_host=st.pm_host)
         K.assign_rr_ext(1, x, n, self.dp, self.cb, self.cnorm, ap, self.xnorm, lab, self.cost_part, st.ub, st.lb,
                         st.mc, st.tau, hist=self.hist, rank=self.rank, delta=dl, gate=st.pmode, want=1, cum=st.cum)
         K.assign_rr_ext(2, x, st.cap_m, self.dp, self.cb, self.cnorm, ap, st.cand_xn, lab, self.cost_part, st.ub,
@@ -1240,10 +1181,10 @@ class LloydEngine:
         dl.accumulate(x, self.dp, lab, 0, self.cost_part, ap.grid, msg, qscale=self._qscale)
 
     def _replay_ok(self) -> bool:
-        """Recorded launch sequences for the device pruned step: eager fused steps (a captured graph already
+        """Recorded launch sequences for the device pruned step: eager steps (a captured graph already
         replays its launches), the sum regime settled (the first step's _sum_grid); CML_KMEANS_REPLAY=0: off."""
         st = self._pst
-        return (st.fused and not self.use_graph and self._grid_done and st.replay is not None
+        return (not self.use_graph and self._grid_done and st.replay is not None
                 and not torch.cuda.is_current_stream_capturing())
 
     def _pdev_post(self) -> None:
@@ -1259,7 +1200,7 @@ class LloydEngine:
 
     def _pdev_post_launches(self, exact: bool) -> None:
         st, k, d = self._pst, self.k, self.d
-        if st.fused and not self.spherical and self.dp <= 2048:
+        if not self.spherical and self.dp <= 2048:
             # K11 + cb_old / cb_cost copies + norms + drifts in one launch, then the centre statistics in one
             K.update_pdev(self.msgs, k, d, self.centers, self.cb, self.dp, self.kp, self.cnorm, self.shift2,
                           self._unit, st.cb_old, st.cb_cost, st.flags, st.cn, st.drift, snap=self._mx)
@@ -1321,68 +1262,18 @@ class LloydEngine:
             K.assign_rr_ext(2, x, st.cap_m, self.dp, self.cb, self.cnorm, ap, st.cand_xn, lab, None, st.ub, st.lb,
                             st.mc, st.tau, delta=dl, idx=st.cand, n_dev=st.count, lab_in=st.cand_lab, gate=st.pmode,
                             want=0, cum=st.cum)
-            if not self._overlap_split(n):
-                K.label_hist(lab, n, ap, self.hist, self.rank, gate=st.pmode, want=0)
+            K.label_hist(lab, n, ap, self.hist, self.rank, gate=st.pmode, want=0)
         self.cost_part.zero_()
         dl.invalidate()
         dl.gate(0)
-        split = self._overlap_split(n)
-        if split:
-            return self._seeded_accumulate_overlapped(split, msg)
         # the seeded upper bounds (r + d1) are loose; the accumulate streams every row anyway and leaves
         # the exact one, |x - c_label| rounded up, so the next step's bounds prove as many rows as after a
         # full pass (the seeded lower bounds stay: d2 - r is far below what they are compared with)
         K.accumulate_sort(x, n, self.dp, d, lab, self.rank, self.hist, ap, k, self.cost_part, self.off, self.seg,
                           self.perm, self.cplan, dl.acc[0], self.slots, gate=dl.mode[0],
-                          ub_centres=self.cb if self._seed_ub else None, ub=st.ub if self._seed_ub else None,
-                          qscale=self._qscale, cum=st.cum)
+                          ub_centres=self.cb, ub=st.ub, qscale=self._qscale, cum=st.cum)
         dl.accumulate(x, self.dp, lab, 0, self.cost_part, ap.grid, msg, qscale=self._qscale)
         self.comm.allreduce_async(msg).wait()
-        self._pdev_post()
-
-    def _overlap_split(self, n: int):
-        """Row ranges of the overlapped full accumulate of the seeded step: two chunks
-        whose sums are all-reduced separately, chunk 0's collective running on the process group's stream
-        while chunk 1 accumulates. Opt-in: multi-rank engines with at least CML_KMEANS_OVERLAP_ROWS local rows
-        (default 0 = off); None otherwise. The second chunk's all-reduce carries the same [k·D | k | 1] message
-        as an unsplit step, so it is exposed just as long — the split hides nothing of a latency-bound
-        collective and pays a second counting sort and accumulate: at the 8-GPU shard (12.5M rows, one-rank
-        RCCL group) the fit took 19.6 ms split against 18.9 ms unsplit (profiles/r6/README.md)."""
-        if not self.comm.is_distributed:
-            return None
-        lim = int(os.environ.get("CML_KMEANS_OVERLAP_ROWS", 0))
-        if lim <= 0 or n < max(lim, 2):
-            return None
-        mid = min(n - 1, max(1, round_up(n // 2, 1024)))
-        return ((0, mid), (mid, n))
-
-    def _seeded_accumulate_overlapped(self, split, msg: torch.Tensor) -> None:
-        """The seeded step's full accumulate in two row chunks, each counting-sorted in its own K9r
-        geometry (label_hist) and summed into its own message; chunk 0's all-reduce is enqueued before
-        chunk 1's accumulate, so it overlaps it. The chunk sums are exact (grid sums: _sum_grid), so their
-        sum is the one-chunk message bit for bit; the incremental-sums state gets the local total."""
-        st, dl, ap = self._pst, self.delta, self.aplan
-        k, d, dp, x, lab = self.k, self.d, self.dp, self.x, self.labels
-        if getattr(self, "_msgs2", None) is None:
-            self._msgs2 = torch.empty((2, self.msg_len), dtype=torch.float64, device=self.device)
-            self._hist2 = torch.empty_like(self.hist)
-        handles = []
-        for c, (r0, r1) in enumerate(split):
-            nc = r1 - r0
-            hist_c = self.hist if c == 0 else self._hist2
-            K.label_hist(lab[r0:r1], nc, ap, hist_c, self.rank[r0:r1])
-            K.accumulate_sort(x[r0:r1], nc, dp, d, lab[r0:r1], self.rank[r0:r1], hist_c, ap, k, self.cost_part,
-                              self.off, self.seg, self.perm, self.cplan, self._msgs2[c], self.slots,
-                              ub_centres=self.cb if self._seed_ub else None,
-                              ub=st.ub[r0:r1] if self._seed_ub else None, qscale=self._qscale, cum=st.cum)
-            if c == 0:
-                dl.acc[0].copy_(self._msgs2[0])  # local sums (before the in-place all-reduce)
-            else:
-                dl.acc[0].add_(self._msgs2[1])
-            handles.append(self.comm.allreduce_async(self._msgs2[c]))
-        for h in handles:
-            h.wait()
-        torch.add(self._msgs2[0], self._msgs2[1], out=msg)
         self._pdev_post()
 
     def _norms64(self) -> torch.Tensor:
@@ -1436,7 +1327,7 @@ class LloydEngine:
         self._ensure_norms()
         if self._pdev:
             return self._pst.mx
-        mx = getattr(self, "_gxmax", None)
+        mx = self._gxmax
         if mx is None:
             mx = (self._xnorm[: self.n].max().reshape(1) if self.n
                   else torch.zeros(1, dtype=torch.float32, device=self.device))
@@ -1491,7 +1382,7 @@ class LloydEngine:
             self._xn64 = (self.x * self.x).sum(1)
             xn = self._xn64
         st.mx = self.comm.max_scalar(float(xn.max()) if n else 0.0)
-        if not self.gpu and getattr(self, "labels", None) is None:
+        if not self.gpu and self.labels is None:
             self.labels = torch.zeros(max(n, 1), dtype=torch.int64)
         self._pst = st
 
@@ -1731,7 +1622,7 @@ class LloydEngine:
 
     def converged(self, tol: float) -> bool:
         """Spark's rule: converged iff every centre moved at most tol (euclidean)."""
-        if self._shift2 is None and getattr(self, "_shift_pair", None) is not None:
+        if self._shift2 is None and self._shift_pair is not None:
             new, old = self._shift_pair  # the screen's one-rank update: the exact path's expression, on demand
             self._shift2 = ((new - old) ** 2).sum(1)
         if self._shift2 is None:
@@ -1811,7 +1702,7 @@ class LloydEngine:
         longer prove, and K9r re-assigns only those (the full pass when there are too many), on copies of
         the labels and bounds — the engine's own step state is untouched. Other paths run a full assign."""
         n, k = self.n, self.k
-        c = getattr(self._scr, "cert", None) if getattr(self, "_scr", None) is not None else None
+        c = getattr(self._scr, "cert", None) if self._scr is not None else None
         if self._screen and n and c is not None and c.valid:
             # certified pruned assign on copies: the bounds moved by the last update's drifts prove most
             # labels; the rest are tightened and re-assigned by the exact fold (same labels as a full pass)
@@ -2197,7 +2088,7 @@ class LloydEngine:
         if as_device and self.gpu:
             return out
         res = out.cpu().numpy()
-        if getattr(self, "_seed", None) is not None and self._seed.out is out:
+        if self._seed is not None and self._seed.out is out:
             self._seed.out_np = res
         return res
 
@@ -2223,7 +2114,7 @@ class LloydEngine:
     def _init_scratch(self):
         """Per-engine scratch of the k-means|| candidate passes (allocated once; the K9r passes write every
         entry they read back, so nothing is cleared per round)."""
-        sc = getattr(self, "_iscr", None)
+        sc = self._iscr
         if sc is None:
             n, dev = self.n, self.device
             tr = self.aplan.round_rows
@@ -2334,7 +2225,7 @@ class LloydEngine:
             c0 += size
         if self.track_prune:
             ca, cb = (int(v) for v in cnt.tolist())
-            self._init_prune_history = getattr(self, "_init_prune_history", []) + [(n, ca, cb)]
+            self._init_prune_history.append((n, ca, cb))
         return True
 
     # Time of one K9r pass over 20M x 256 bf16 rows by centre tiles per compute wave (64 centres each),
@@ -2355,7 +2246,7 @@ class LloydEngine:
     def _rr_max_chunk(self) -> int:
         """Most centres one K9r launch takes at this row width (320 at Dp = 256 bf16, 128 at Dp = 512:
         (k/64)·(Dp/32) bounded by the compute waves' VGPRs); 0 when K9r does not apply."""
-        if getattr(self, "_rr_max", None) is None:
+        if self._rr_max is None:
             self._rr_max = 0
             for c in (320, 256, 192, 128, 64):
                 p = K.plan_assign(1, self.dp, c, fp8=K.is_fp8(self.x))

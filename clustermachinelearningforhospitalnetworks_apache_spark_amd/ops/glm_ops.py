@@ -232,7 +232,7 @@ def multinomial_grad(x: torch.Tensor, d: int, y: torch.Tensor, coef: torch.Tenso
     with d <= 256, d % 8 == 0, and on e4m3 rows with d % 16 == 0 (widened exactly to bf16 as they are staged in
     LDS) (glm_mfma.hip: both products on
     v_mfma_f32_32x32x16_bf16 with the f32 operand — weights, residuals — split into three bf16 terms, so f32
-    precision; ``set_multinomial_mfma_mode(1)`` selects the v_mfma_f32_32x32x2_f32 form), else the VALU kernel
+    precision), else the VALU kernel
     (multinomial_grad_kernel: X read once, gradient partials in f64, fixed-order reduction) where its layout fits
     (C <= 8, d up to 512; also ``prefer_valu=True``); otherwise — and on the CPU — row chunks in f64 (never an f64 copy of the whole X)."""
     C = int(coef.shape[0])
@@ -306,8 +306,9 @@ def multinomial_predict(x: torch.Tensor, d: int, coef: torch.Tensor):
 
 def set_multinomial_mfma_mode(mode: int) -> int:
     """K13m MFMA form: 0 = bf16 three-term products (default; C <= 16 on a 16-class tile of 16x16x32 MFMAs),
-    1 = f32 MFMAs, 2 = bf16 with W split in registers on every use, 3 = mode 0 on 32-class tiles of 32x32x16
-    MFMAs for every C (A/B). Returns the previous mode."""
+    2 = W split in registers on every use, on 32-class tiles for every C (what the default runs where the split
+    planes do not fit in LDS; the test route to it at small shapes). A negative mode queries; any other value
+    leaves the mode unchanged. Returns the previous mode."""
     return int(_native.kernels().cml_multinomial_mfma_set_mode(int(mode)))
 
 

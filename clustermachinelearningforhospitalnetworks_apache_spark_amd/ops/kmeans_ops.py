@@ -23,7 +23,6 @@ _native.register_kernel_sigs({
     "cml_kmeans_assign_lds_bytes": (c_ll, [c_int, c_int, c_int]),
     "cml_kmeans_assign_threads": (c_int, [c_int]),
     "cml_kmeans_set_assign_variant": (c_int, [c_int]),
-    "cml_kmeans_set_assign_sched": (c_int, [c_int]),
     "cml_kmeans_assign_occupancy": (c_int, [c_int, c_int, c_int, c_int]),
     "cml_kmeans_seg_threads": (c_int, []),
     "cml_kmeans_seg_ints": (c_ll, [c_int]),
@@ -35,7 +34,6 @@ _native.register_kernel_sigs({
     "cml_kmeans_set_rr_debug": (c_int, [c_int]),
     "cml_kmeans_set_rr_m32": (c_int, [c_int]),
     "cml_kmeans_set_fp8_mx": (c_int, [c_int]),
-    "cml_kmeans_set_delta_fused_fixup": (c_int, [c_int]),
     "cml_kmeans_assign_tile_rows": (c_int, [c_int]),
     "cml_row_sqnorm_bf16": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_vp]),
     "cml_row_sqnorm_fp8": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_vp]),
@@ -448,9 +446,6 @@ def _apply_env_knobs(lib) -> None:
         _native.check(lib.cml_kmeans_set_rr_m32(int(m32)), "set_rr_m32")
     if os.environ.get("CML_KMEANS_FP8_MX") == "0":
         lib.cml_kmeans_set_fp8_mx(0)
-    fx = os.environ.get("CML_DELTA_FUSED_FIXUP")
-    if fx:  # incremental sums: cross-slice partials added by the apply instead of a fixup launch (A/B)
-        lib.cml_kmeans_set_delta_fused_fixup(int(fx))
 
 
 def plan_assign(n: int, dp: int, k: int, device_index: int = 0, fp8: bool = False) -> AssignPlan:
@@ -482,14 +477,15 @@ def plan_assign(n: int, dp: int, k: int, device_index: int = 0, fp8: bool = Fals
 
 
 def set_assign_variant(v: int) -> None:
-    """Tuning knob for the K9 launch shape (0 auto, 1 one wave/SIMD, 2 two waves/SIMD, ..., 6 default shape with
-    per-sub-tile accumulator seeding, 7 PACK4 keys, 8 K9r register-resident centres + LDS-DMA X ring).
+    """Test hook for the assign kernel choice: 0 automatic (K9r wherever it applies, see set_rr_default, else
+    K9 in its default launch shape), 1-3 K9 launch shapes (1 = two 16-row sub-tiles + X double buffer, 2 = one
+    sub-tile, 3 = four), 8 forces K9r (register-resident centres + LDS-DMA X ring). Any other value is an error.
     Plans made before a change keep the kernel they were made for."""
     _native.check(_native.kernels().cml_kmeans_set_assign_variant(int(v)), "set_assign_variant")
 
 
 def set_rr_default(on: bool) -> None:
-    """Whether variant 0 (auto) picks K9r wherever it applies."""
+    """Whether variant 0 (auto) picks K9r wherever it applies; off, variant 0 is the K9 fallback at every shape."""
     _native.check(_native.kernels().cml_kmeans_set_rr_default(int(bool(on))), "set_rr_default")
 
 
@@ -497,11 +493,6 @@ def set_rr_m32(on: bool) -> None:
     """K9r compute waves on 32x32x16 MFMA tiles (even centre-tile counts; CML_KMEANS_RR_M32=1) or the
     16x16x32 form (default, faster on MI355X). Both give the same labels up to the distance rounding."""
     _native.check(_native.kernels().cml_kmeans_set_rr_m32(int(bool(on))), "set_rr_m32")
-
-
-def set_assign_sched(v: int) -> None:
-    """Tuning knob: partner-wave desynchronisation of K9 (bit 0 priority, bit 1 + v>>2 stagger)."""
-    _native.check(_native.kernels().cml_kmeans_set_assign_sched(int(v)), "set_assign_sched")
 
 
 def plan_accum(n: int, dp: int, k: int, device_index: int = 0, force: str | None = None,

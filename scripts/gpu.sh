@@ -12,8 +12,6 @@
 #                         kernel / blocking-call / roctx timeline, kernel table, host syncs, sync audit
 #   strong                strong-scaling emulation: per-rank shards of the headline (100M / N rows)
 #   workflow              the reference workflow end to end on 4M uploaded rows (examples/)
-#   ovtl [seeded|full]    2-rank gloo timeline of the seeded step's overlapped accumulate, or of the split
-#                         full-pass step on overlapping data (rocprofv3 per rank)
 #   clock                 K9r clock / MFMA busy share, rows from HBM vs from L2 (one rocprofv3 --pmc pass)
 #   drivers               every scripts/mb_*.py subcommand once at a small size, prof.py on a fresh trace
 #   mb SCRIPT [args]      a microbenchmark script (scripts/mb_*.py ...) -> SCRIPT.log
@@ -125,23 +123,6 @@ h.synth_uploads('/tmp/wfsrc/hospitals/incoming', n_files=4, rows=1000000)
   python3 -c "print('workflow wall s', round($t1 - $t0, 3))"
   grep -A24 "^range" "$O/workflow.log"
   ;;
-ovtl)
-  # two gloo ranks on the one GPU, one rocprofv3 process each: the seeded step's split accumulate and the
-  # order of chunk 0's all-reduce copies against chunk 1's kernels (scripts/overlap_timeline.py)
-  P=$((29500 + RANDOM % 400))
-  W=${1:-seeded}  # seeded | full
-  timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/ov0 -o r0 -- \
-    python3 scripts/overlap_timeline.py rank 0 2 $P $W > "$O/r0.log" 2>&1 &
-  P0=$!
-  S1=0
-  timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/ov1 -o r1 -- \
-    python3 scripts/overlap_timeline.py rank 1 2 $P $W > "$O/r1.log" 2>&1 || S1=$?
-  S0=0
-  wait $P0 || S0=$?
-  [ $S0 -eq 0 ] && [ $S1 -eq 0 ] || { tail -20 "$O/r0.log" "$O/r1.log"; exit 1; }
-  python3 scripts/overlap_timeline.py show /tmp/ov0/r0_results.db /tmp/ov1/r1_results.db > "$O/timeline.txt"
-  head -80 "$O/timeline.txt"
-  ;;
 clock)
   # K9r clock and MFMA busy share with rows from HBM vs from L2 (one PMC pass, kernel trace only)
   R=$PWD
@@ -159,8 +140,6 @@ drivers)
   $M dbg 2000000 > $O/dbg.log 2>&1 && tail -3 $O/dbg.log &&
   $M modes 2000000 > $O/modes.log 2>&1 && tail -3 $O/modes.log &&
   $M pmc-mode 2000000 256 256 1 > $O/pm.log 2>&1 && tail -1 $O/pm.log &&
-  $M sched 2000000 0,1 > $O/sched.log 2>&1 && tail -3 $O/sched.log &&
-  $M ablate 0 8 > $O/ablate.log 2>&1 && tail -3 $O/ablate.log &&
   (cd /tmp && timeout -k 10 180 rocprofv3 --kernel-trace -d /tmp/drv -o p -- python3 "$R/scripts/mb_k9r.py" pmc 8 2000000) > $O/prof.log 2>&1 &&
   python3 scripts/prof.py stats /tmp/drv/p_results.db --top 5 > $O/stats.txt && cat $O/stats.txt &&
   bash scripts/gpu.sh clock "${O#gpurun_out/}/clock" &&

@@ -2,7 +2,8 @@
 subcommand per experiment. Positional arguments default to the headline shape, 20M x 256 bf16, k = 256.
 
     python scripts/mb_k9r.py rr [N D K [VARIANTS [fp8]]]
-        in-process A/B of assign variants (0 = K9, 8 = K9r, 9 = K9 with the K9r default off), alternated round by
+        in-process A/B of assign variants (0 = automatic, 1-3 = K9 launch shapes, 8 = K9r, 9 = K9 with the K9r
+        default off), alternated round by
         round so DVFS drift hits all; full pass and compute-only pass (every row aliases row 0: no HBM stream)
     python scripts/mb_k9r.py dbg [N D K [fp8]]
         K9r ablation by its `dbg` bits (1 no LDS-DMA, 2 no MFMA/keys, 4 no finalize, and their unions);
@@ -11,7 +12,8 @@ subcommand per experiment. Positional arguments default to the headline shape, 2
         the K9r modes: 0 (assign + counting-sort ranks), 1 (top-2 bounds), 2 (candidate rows at 2/5/20 %), the
         fused row pass, and the centre tiles per wave for k = 64..320
     python scripts/mb_k9r.py pmc [VARIANT N D K DBG]
-        dispatches for a PMC pass: 3 full passes then 3 compute-only passes (identify them by order)
+        dispatches for a PMC pass of a variant (as in rr): 3 full passes then 3 compute-only passes
+        (identify them by order)
     python scripts/mb_k9r.py pmc-mode [N D K MODE]
         3 launches of K9r mode 0 or mode 1 (top-2) for a PMC pass
     python scripts/mb_k9r.py clock
@@ -19,10 +21,6 @@ subcommand per experiment. Positional arguments default to the headline shape, 2
         under rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES)
     python scripts/mb_k9r.py clock-show DIR
         per-dispatch clock and MFMA busy share from that run's counter CSV (no GPU)
-    python scripts/mb_k9r.py ablate [VARIANTS]
-        K9 launch variants (kmeans_ops.set_assign_variant): full vs compute-only vs a 32-centre launch, three shapes
-    python scripts/mb_k9r.py sched [N [SCHEDS]]
-        K9 pass time vs partner-wave scheduling (kmeans_ops.set_assign_sched), plus its compute and memory bounds
 """
 import csv
 import glob
@@ -91,6 +89,14 @@ def wall_ms(fn, reps=7):
     return 1000 * sorted(ts)[reps // 2]
 
 
+def _set_variant(K, v):
+    """0 = automatic, 1-3 = K9 launch shapes, 8 = K9r forced, 9 = K9 (automatic with the K9r default off)."""
+    if v not in (0, 1, 2, 3, 8, 9):
+        raise SystemExit(f"assign variant {v}: 0, 1, 2, 3, 8 or 9")
+    K.set_assign_variant(0 if v == 9 else v)
+    K.set_rr_default(v != 9)
+
+
 def cmd_rr(argv):
     torch, _, _, _, K = _env()
     n, d, k = _arg(argv, 0, 20_000_000), _arg(argv, 1, 256), _arg(argv, 2, 256)
@@ -100,8 +106,7 @@ def cmd_rr(argv):
     print(f"n={n} d={d} (padded {eng.dp}) k={k} {'fp8' if fp8 else 'bf16'}", flush=True)
     plans = {}
     for v in variants:
-        K.set_assign_variant(0 if v == 9 else v)
-        K.set_rr_default(v != 9)
+        _set_variant(K, v)
         plans[v] = K.plan_assign(n, eng.dp, k, fp8=fp8)
     K.set_assign_variant(0)
     K.set_rr_default(True)
@@ -233,7 +238,7 @@ def cmd_pmc(argv):
     torch, _, _native, _, K = _env()
     v, n, d, k, bits = (_arg(argv, 0, 0), _arg(argv, 1, 20_000_000), _arg(argv, 2, 256), _arg(argv, 3, 256),
                         _arg(argv, 4, 0))
-    K.set_assign_variant(v)
+    _set_variant(K, v)
     if bits:
         _native.kernels().cml_kmeans_set_rr_debug(bits)
     eng, x0 = engine(n, d, k)
@@ -303,69 +308,8 @@ def cmd_clock_show(argv):
               f"SQ_BUSY_CYCLES {d.get('SQ_BUSY_CYCLES', 0):.3g}")
 
 
-def cmd_ablate(argv):
-    torch, _, _, _, K = _env()
-    variants = [int(v) for v in argv] or [0, 1, 2, 3, 4, 5]
-    for n, d, k in ((20_000_000, 256, 256), (20_000_000, 16, 5), (10_000_000, 128, 64)):
-        x = torch.randn(n, d, device="cuda", dtype=torch.bfloat16)
-        dp = x.shape[1]
-        xn = K.row_sqnorm(x, n, dp)
-        for kk in sorted({k, 32}, reverse=True):
-            kp = (kk + 31) // 32 * 32
-            cb = torch.randn(kp, dp, device="cuda").to(torch.bfloat16)
-            cn = (cb.float() ** 2).sum(1)
-            lab = torch.empty(n, dtype=torch.int32, device="cuda")
-            for v in variants:
-                K.set_assign_variant(v)
-                ap = K.plan_assign(n, dp, kk)
-                cost = torch.zeros(ap.grid, dtype=torch.float64, device="cuda")
-                best = torch.empty(n, device="cuda") if -(-kp // ap.kc) > 1 else None
-                for xx, tag in ((x, "full"), (torch.as_strided(x, (n, dp), (0, 1)), "ldx0")):
-                    if tag == "ldx0" and kk != k:
-                        continue
-
-                    def run():
-                        K.assign_bf16(xx, n, dp, cb, cn, ap, lab, best, cost, xnorm=xn)
-                    run()
-                    t = min(event_ms(run))
-                    print(f"n={n} d={d} k={kk} v{v} grid={ap.grid}x{ap.nwaves}w {tag:5s}: {t:.3f} ms "
-                          f"{n * dp * 2 / t / 1e9:.2f} TB/s {2 * n * dp * kp / t / 1e9:.0f} TF/s", flush=True)
-        K.set_assign_variant(0)
-        del x, xn
-        torch.cuda.empty_cache()
-
-
-def cmd_sched(argv):
-    torch, _, _, KM, K = _env()
-    n = _arg(argv, 0, 20_000_000)
-    scheds = [int(v) for v in argv[1].split(",")] if len(argv) > 1 else [0, 1, 18, 34, 66, 35, 0]
-    eng, x0 = engine(n, 256, 256)
-    eng.step()
-    for sc in scheds:
-        K.set_assign_sched(sc)
-        assign(eng, eng.x)
-        torch.cuda.synchronize()
-        ts = sorted(event_ms(lambda: assign(eng, eng.x), 7))
-        t = ts[3]
-        print(f"sched {sc:3d}: median {t:.3f} ms (min {ts[0]:.3f}) -> {2 * n * 256 * 256 / t / 1e9:.0f} TF/s, "
-              f"{n * 512 / t / 1e9:.2f} TB/s", flush=True)
-    K.set_assign_sched(0)
-    t = sorted(event_ms(lambda: assign(eng, x0), 7))[3]
-    print(f"compute-only (ldx=0): median {t:.3f} ms -> {2 * n * 256 * 256 / t / 1e9:.0f} TF/s", flush=True)
-    e32 = KM.LloydEngine(eng.x[:, :256], 256, 32, use_graph=False)
-    e32.set_centers(eng.x[:32, :256].to(torch.float32).double().cpu().numpy())
-    e32.step()
-
-    def run32():
-        K.assign_bf16(e32.x, n, e32.dp, e32.cb, e32.cnorm, e32.aplan, e32.labels, None, e32.cost_part, None, None,
-                      xnorm=e32.xnorm)
-    run32()
-    t = sum(event_ms(run32)) / 5
-    print(f"k=32 (memory-bound): {t:.3f} ms -> {n * 512 / t / 1e9:.2f} TB/s", flush=True)
-
-
 COMMANDS = {"rr": cmd_rr, "dbg": cmd_dbg, "modes": cmd_modes, "pmc": cmd_pmc, "pmc-mode": cmd_pmc_mode,
-            "clock": cmd_clock, "clock-show": cmd_clock_show, "ablate": cmd_ablate, "sched": cmd_sched}
+            "clock": cmd_clock, "clock-show": cmd_clock_show}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:

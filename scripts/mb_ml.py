@@ -327,16 +327,15 @@ def cmd_multinomial(argv):
         y = torch.randint(0, C, (n,), generator=g, device=dev).to(torch.float64)
         coef = torch.randn(C, d + 1, generator=g, device=dev, dtype=torch.float64) * 0.05
         # MFMA form: margins + gradient on the padded class tile (16, 32 or 64 classes)
-        flop = 4.0 * n * d * (16 if C <= 16 else 32 if C <= 32 else 64)  # (mode 3: 32 for C <= 16 too)
+        flop = 4.0 * n * d * (16 if C <= 16 else 32 if C <= 32 else 64)  # (mode 2: 32 for C <= 16 too)
         runs = []
         if lib.cml_multinomial_supported(d, code, C) > 0:
             runs.append(("valu", lambda: glm_ops.multinomial_grad(x, d, y, coef, prefer_valu=True)))
         cp = lib.cml_multinomial_mfma_supported(d, code, C)
-        if cp > 0:  # every MFMA form (mode 0, the first, is the default route)
+        if cp > 0:  # both MFMA forms (mode 0, the first, is the default route)
             dp = lib.cml_multinomial_mfma_dpad(d, C)
-            for mode, name in ((0, "mfma-bf16x3"), (3, "mfma-bf16x3-32tile"), (2, "mfma-bf16x3-regsplit"),
-                               (1, "mfma-f32")):
-                if (mode == 3 and C > 16) or (code == 3 and mode in (1, 2)):  # (e4m3 rows: bf16 forms only)
+            for mode, name in ((0, "mfma-bf16x3"), (2, "mfma-bf16x3-regsplit")):
+                if code == 3 and mode == 2:  # (e4m3 rows: the default split only)
                     continue
                 runs.append((name, (lambda m: lambda: _mode_run(m, x, d, y, coef, C, cp, dp))(mode)))
         if not runs:

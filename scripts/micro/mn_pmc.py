@@ -1,5 +1,6 @@
 """Workload for one rocprofv3 --pmc pass over the K13m MFMA forms (100M x 256 bf16 rows, C = 8): the 16-class
-tile (mode 0) and the 32-class tile (mode 3), three dispatches each, in that order.
+tile with W pre-split in LDS (mode 0) and the 32-class tile with W split on the fly (mode 2), three dispatches each,
+in that order.
 
     cd /tmp && rocprofv3 --pmc <counters> --kernel-trace --output-format csv -d /tmp/pm -o pm -- \
         python3 $REPO/scripts/micro/mn_pmc.py
@@ -23,7 +24,7 @@ g.manual_seed(1)
 y = torch.randint(0, C, (n,), generator=g, device=dev).double()
 coef = torch.randn(C, d + 1, generator=g, device=dev, dtype=torch.float64) * 0.05
 lib = _native.kernels()
-for mode in (0, 3):
+for mode in (0, 2):
     prev = glm_ops.set_multinomial_mfma_mode(mode)
     cp, dp = lib.cml_multinomial_mfma_supported(d, 0, C), lib.cml_multinomial_mfma_dpad(d, C)
     for _ in range(3):

@@ -133,16 +133,13 @@ def _rank_main2(rank, world, port, out_path, use_graph=True):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("use_graph,overlap", [(False, False), (True, False), (False, True)])
+@pytest.mark.parametrize("use_graph,overlap", [(False, False), (True, False)])
 def test_two_ranks_default_path_match_single_rank(tmp_path, monkeypatch, use_graph, overlap):
     """Two ranks on the default GPU path (pruned init, seeded step, eager pruned steps around the
     all-reduce — or split graphs) give the single-rank fit bit for bit: init centres, final centres and
-    cost (1/8-grid data: every f64 sum is exact). ``overlap``: the seeded step's full accumulate in two
-    chunks whose all-reduces overlap the next chunk (forced on at this size) — the same bits."""
+    cost (1/8-grid data: every f64 sum is exact)."""
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.parallel.comm import local_comm
     monkeypatch.setenv("CML_KMEANS_PRUNE", "1")
-    if overlap:
-        monkeypatch.setenv("CML_KMEANS_OVERLAP_ROWS", "1")
     out = str(tmp_path / "w2d.json")
     ctx = mp.get_context("spawn")
     port = _free_port()
@@ -298,9 +295,8 @@ def test_bench_two_rank_launch_on_one_gpu():
     assert res["steps"] == 3 and res["value"] > 0 and res["extra"]["iterations"] == 3
 
 
-# ---- the split full-pass step: on data the bounds cannot prune, each full-pass step runs in
-# two row chunks and chunk 0's all-reduce is in flight during chunk 1's K9r pass; A + B must be the one-message
-# step bit for bit, on two ranks and against one rank
+# ---- full-pass steps on two ranks: on data the bounds cannot prune the gate keeps picking the full pass (the
+# lagged host hint then enqueues the full-accumulate launches); two ranks must give the one-rank fit bit for bit
 
 N3, D3, K3 = 240_000, 128, 64
 
@@ -317,16 +313,17 @@ def _fit3(x_local, comm):
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import LloydEngine
     eng = LloydEngine(torch.as_tensor(x_local, device="cuda").to(torch.bfloat16), D3, K3, comm, prune=True,
                       precision="bf16")
+    eng.track_prune = True
     eng.set_centers(eng.init_kmeans_parallel(seed=2))
     eng.fit(12, 0.0)
     torch.cuda.synchronize()
     return {"centers": eng.centers.cpu().numpy().tolist(), "cost": eng.training_cost(),
-            "split": int(getattr(eng._pst, "split_steps", 0)), "pdev": bool(eng._pdev)}
+            "hist": eng.prune_history(), "pdev": bool(eng._pdev)}
 
 
 def _rank_main3(rank, world, port, out_path):
     os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1",
-                       "MASTER_PORT": str(port), "CML_KMEANS_OVERLAP_ROWS": "1", "CML_KMEANS_SPLIT_FULL": "1"})
+                       "MASTER_PORT": str(port)})
     import torch
     import torch.distributed as dist
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.parallel.comm import Communicator
@@ -342,7 +339,7 @@ def _rank_main3(rank, world, port, out_path):
     dist.destroy_process_group()
 
 
-def test_split_full_pass_steps_two_ranks_match_single_rank(tmp_path, monkeypatch):
+def test_full_pass_steps_two_ranks_match_single_rank(tmp_path):
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.parallel.comm import local_comm
     out = str(tmp_path / "w3")
     ctx = mp.get_context("spawn")
@@ -354,17 +351,10 @@ def test_split_full_pass_steps_two_ranks_match_single_rank(tmp_path, monkeypatch
         p.join(240)
     assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
     res = [json.load(open(f"{out}.{r}")) for r in range(2)]
-    monkeypatch.setenv("CML_KMEANS_SPLIT_FULL", "0")
     ref = _fit3(_data3(), local_comm())
-    assert ref["pdev"] and ref["split"] == 0
+    assert ref["pdev"]
     for r in range(2):
-        assert res[r]["split"] > 0, res[r]["split"]  # the overlapped steps ran
+        # the full-pass branch ran on this rank after the first step (history: (full?, re-assigned rows) per step)
+        assert res[r]["pdev"] and any(full for full, _ in res[r]["hist"][1:]), res[r]["hist"]
         np.testing.assert_array_equal(np.asarray(res[r]["centers"]), np.asarray(ref["centers"]))
         assert res[r]["cost"] == ref["cost"]
-    # and on one rank: the split step (forced) is the one-message step bit for bit
-    monkeypatch.setenv("CML_KMEANS_SPLIT_FULL", "1")
-    monkeypatch.setenv("CML_KMEANS_OVERLAP_ROWS", "1")
-    one = _fit3(_data3(), local_comm())
-    assert one["split"] > 0
-    np.testing.assert_array_equal(np.asarray(one["centers"]), np.asarray(ref["centers"]))
-    assert one["cost"] == ref["cost"]
