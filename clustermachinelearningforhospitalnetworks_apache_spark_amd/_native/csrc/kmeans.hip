@@ -1840,6 +1840,26 @@ static int sort_accum(const void* X, long long n, long long ldx, int Dp, int D, 
   return launch_segsum(X, n, ldx, Dp, D, perm, seg, k, cpl, seg_grid, msg, slots, slot_c, xfp8, gate, want, st, sub);
 }
 
+// The counting sort alone (totals + offsets + scatter, no segmented sum): perm = the row ids in label order,
+// seg[c] = the first sorted position of cluster c (seg[k] = n), for a consumer with sums of its own (the
+// weighted sums of kmeans_weighted.hip). hist / rank / nblk / round_rows as cml_kmeans_sort_accum; `seg` holds
+// cml_kmeans_seg_ints(k) ints; `tail` f64 [k + 1] receives the row count of every cluster, then Σ cost_part.
+CML_API int cml_kmeans_sort_perm(long long n, const int* labels, const int* rank, const int* hist, int nblk,
+                                 int round_rows, int k, int kp, const double* cost_part, int ncost, int* off, int* seg,
+                                 int* perm, double* tail, void* stream) {
+  if (k <= 0 || nblk <= 0 || n < 0 || tail == nullptr) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  long long* tot = reinterpret_cast<long long*>(seg + k + 1 + ((k + 1) & 1));  // scratch after seg (8-B aligned)
+  hipLaunchKernelGGL(kmeans_seg_totals, dim3(k), dim3(256), 0, st, hist, nblk, kp, tot, (const int*)nullptr, 1);
+  hipLaunchKernelGGL(kmeans_seg_offsets, dim3(k), dim3(256), 0, st, hist, nblk, k, kp, tot, cost_part,
+                     cost_part != nullptr ? ncost : 0, /*D=*/0, off, seg, tail, (const int*)nullptr, 1);
+  int e = cml_status();
+  if (e || n == 0) return e;
+  hipLaunchKernelGGL(kmeans_scatter, dim3(nblk), dim3(kScatterThreads), sizeof(int) * (size_t)k, st, labels, rank, n,
+                     nblk, 1, round_rows, k, off, perm, (const int*)nullptr, 1);
+  return cml_status();
+}
+
 // ---- incremental sums (see kmeans_delta_gate). Per step, after the single-launch assign that
 // logged label changes: cml_kmeans_delta_gate, then cml_kmeans_sort_accum(gate = mode, msg = acc),
 // then cml_kmeans_delta_accum (which also publishes msg = acc).

@@ -27,6 +27,14 @@ assigned centre is carried across iterations (Hamerly), so rows whose bound prov
 read at all and only the others are re-assigned against every centre. Labels, sums and centres are
 those of the full step (tests/test_kmeans_prune.py); the headline bench keeps the full assignment.
 
+Weighted fits (``weights``, Spark's weightCol) run the source-precision path by default; with
+``precision="bf16"`` device rows stay bf16 / e4m3 and the step is K9 / K9r, the counting sort and the
+weighted double-double sums of ``kmeans_weighted.hip`` (``_step_weighted``): unpruned, full steps, one
+row chunk. Its sums are the exact sums of the rounded products fl64(w·x), correctly rounded, so they do
+not depend on the order, the slicing or the number of ranks while the products of a column span fewer
+than about 106 - 53 - ceil(log2 n) binary orders (the source-precision weighted sums' own contract);
+beyond that the result is still deterministic for a fixed partition.
+
 CPU tensors run the same algorithm with torch float64 ops (``local[n]`` mode and
 the numerical oracle).
 """
@@ -222,13 +230,23 @@ class LloydEngine:
         self.refresh_interval = max(0, int(refresh_interval))
         # weights (Spark's weightCol, KMeans.scala runAlgorithm): centre = Σ w·x / Σ w, cost = Σ w·d²,
         # k-means|| candidates weighted by the summed weight of their rows. Weighted fits run the
-        # source-precision path (f64 rows, deterministic f64 sums of [w·x | w]).
+        # source-precision path (f64 rows, deterministic f64 sums of [w·x | w]) unless precision "bf16" is
+        # asked for (argument, conf cml.ml.kmeans.precision, env CML_KMEANS_PRECISION): device rows then
+        # stay bf16 / e4m3 on the MFMA path (_step_weighted: K9 / K9r assign, the counting sort, the
+        # double-double weighted sums of K10w — the same correctly rounded Σ fl64(w·x) the source-precision
+        # path forms, with no f64 copy of X). "auto" keeps the source-precision routing; host rows with
+        # "bf16" take the host path, as an unweighted "bf16" request on host rows does.
+        self._wfast = False
         if weights is not None:
-            if str(precision or "auto").lower() == "bf16":
-                raise ValueError("weighted KMeans runs at source precision; precision 'bf16' is not supported")
-            precision, prune = "exact", False
-            if x.is_cuda and x.dtype not in (torch.float32, torch.float64):
-                x = x.to(torch.float32)
+            req = str(precision or os.environ.get("CML_KMEANS_PRECISION") or "auto").lower()
+            if req == "bf16" and x.is_cuda:
+                self._wfast = True
+                precision, prune, incremental, use_graph = "bf16", False, False, False
+                row_chunks, accum_mode = 1, "sort"
+            else:
+                precision, prune = "exact", False
+                if x.is_cuda and x.dtype not in (torch.float32, torch.float64):
+                    x = x.to(torch.float32)
         # precision (cml.ml.kmeans.precision): "bf16" = the MFMA path (bf16 rows in the distance GEMM,
         # exact f64 sums of those rows); "exact" = the f64 reference algorithm on the rows as given
         # (kmeans_exact.hip on the GPU); "auto" = exact for f32/f64 device rows — the reference's f64
@@ -327,8 +345,17 @@ class LloydEngine:
             w = torch.as_tensor(weights, dtype=torch.float64, device=self.device).reshape(-1)
             if w.shape[0] != self.n:
                 raise ValueError(f"{w.shape[0]} weights for {self.n} rows")
-            self.w = w
-            self._wx = torch.cat([self.x * w[:, None], w[:, None]], 1)  # [w·x | w]: one sums pass
+            self.w = w.contiguous()
+            if self._wfast:  # K10w reads the rows as they are: no f64 copy of X, no [w·x | w]
+                fp8 = K.is_fp8(self.x)
+                # (K10w itself takes e4m3 rows up to 1024 columns; the assign kernels stop at 512)
+                if (fp8 and not 256 <= self.dp <= 512) or (not fp8 and self.dp > 512):
+                    raise ValueError(
+                        f"weighted KMeans with precision 'bf16' assigns on the MFMA kernels and sums in the sort "
+                        f"regime: padded width {self.dp} is outside their limit (bf16 rows Dp <= 512, e4m3 rows "
+                        f"256 <= Dp <= 512); use precision 'auto' for the source-precision path")
+            else:
+                self._wx = torch.cat([self.x * w[:, None], w[:, None]], 1)  # [w·x | w]: one sums pass
         # error allowance of the assign's squared distances (pruning bounds), scaled with the padded
         # width: the f32 accumulation error grows with D; f64 rows keep the fixed floor
         # fp8 rows: the K9r passes run MX-scaled fp8 MFMAs against an exact e4m3 split of the centres, which
@@ -367,6 +394,7 @@ class LloydEngine:
         self._shift_pair = None
         self._iscr = None  # scratch of the k-means|| candidate passes (_init_scratch)
         self._rr_max = None  # _rr_max_chunk
+        self._wst = None  # buffers of the weighted MFMA step (_step_weighted)
         self._init_prune_history = []  # (rows, per-row path, K9r pass) of the pruned k-means|| rounds (track_prune)
         if self.gpu:
             self._alloc_gpu()
@@ -586,6 +614,8 @@ class LloydEngine:
                 self._pst.history.append(self._pdev_last())
         elif self.prune:
             self._step_prune()
+        elif self._wfast:
+            self._step_weighted()
         elif self.gpu and self.use_graph and not self.comm.is_distributed:
             self._step_graph()
         elif self.gpu:
@@ -609,6 +639,8 @@ class LloydEngine:
             return
         self._grid_done = True
         if not self.gpu or K.is_fp8(self.x) or self.cplan.mode != "sort" or (self.prune and not self._pdev):
+            return
+        if self._wfast:  # double-double sums of the products need no grid
             return
         if self._erange is None:  # norms came from a cache without the range: one more pass for it
             er = torch.tensor([2 ** 31 - 1, -1], dtype=torch.int32, device=self.device)
@@ -732,6 +764,51 @@ class LloydEngine:
             K.update_centers(None, self.k, self.d, self.centers, self.cb, self.dp, self.kp, self.cnorm, None,
                              snap=self._mx)
         self._shift2 = self.shift2
+
+    def _step_weighted(self):
+        """One weighted Lloyd iteration on the MFMA path (weights with precision "bf16"): the unweighted
+        step's assign (K9 / K9r with the counting sort's hist / rank) and sort, then K10w instead of the f64
+        segmented sums: per cluster Σ fl64(w·x), Σ w and Σ fl64(w·||x||²) in double-double, read from the
+        bf16 / e4m3 rows as they are. Several ranks gather [S | S_lo] and fold them in rank order
+        (_exact_global's scheme), so the message — and every centre — is the one-rank bits for any split of
+        the rows. K11 runs unchanged on [Σw·x | Σw | 0]: it divides by the count slot, here W_j, and keeps
+        the centre of a cluster with W_j = 0. The cost is evaluated on first read from the same sums
+        (_weighted_cost), with no pass over X."""
+        n, k, d, dev = self.n, self.k, self.d, self.device
+        st = self._wst
+        if st is None:
+            f64 = dict(dtype=torch.float64, device=dev)
+            st = self._wst = types.SimpleNamespace(
+                S=torch.zeros((k, d + 2), **f64), S_lo=torch.zeros((k, d + 2), **f64),
+                tail=torch.zeros(k + 1, **f64), q=torch.zeros(k, **f64),
+                slots=K.wseg_slots(self.cplan, d, dev))
+        if n:
+            K.assign_bf16(self.x, n, self.dp, self.cb, self.cnorm, self.aplan, self.labels, self._best(0, n),
+                          self.cost_part, self.hist, self.rank, xnorm=self.xnorm[:n])
+            K.sort_perm(self.labels, self.rank, self.hist, self.aplan, n, k, self.off, self.seg, self.perm,
+                        tail=st.tail)
+            K.weighted_sums(self.x, n, self.dp, d, self.w, self._norms64(), k, self.perm, self.seg, self.cplan,
+                            out=(st.S, st.S_lo), slots=st.slots)
+        S = st.S
+        if self.comm.is_distributed:
+            m = S.numel()
+            g = self.comm.allgather_fixed(torch.cat([st.S.reshape(-1), st.S_lo.reshape(-1)]))
+            S = K.dd_fold(g[:, :m], g[:, m:]).reshape(k, d + 2)
+        msg = self.msgs[0]
+        msg[:k * d].view(k, d).copy_(S[:, :d])
+        msg[k * d:k * d + k].copy_(S[:, d])
+        msg[k * d + k:].zero_()
+        st.q.copy_(S[:, d + 1])
+        self._cb_cost.copy_(self.cb)
+        self._cost_fn = self._weighted_cost
+        self._update_gpu(self.msgs)
+
+    def _weighted_cost(self) -> torch.Tensor:
+        """Σ w_i |x_i - c_label(i)|² of the last weighted step's assignment, from its sums alone:
+        Σ_j (Q_j - 2 c_j·S_j + W_j |c_j|²) with Q_j = Σ fl64(w_i ||x_i||²), S_j and W_j the (rank-folded)
+        weighted sums and c_j the bf16 centres the assignment compared with. No collective: every rank
+        holds the folded sums."""
+        return K.cost_combine(self._wst.q, self.msgs, self.k, self.d, 1.0, self._cb_cost)
 
     # ------------------------------------------------------------------ MFMA-screened exact assignment
     @staticmethod
@@ -1647,6 +1724,11 @@ class LloydEngine:
             if on_iter is not None:
                 on_iter(it)
             if tol > 0 and self.converged(tol):
+                break
+            # the weighted MFMA step at tol = 0: a step that moved no centre is a fixed point (the next
+            # assignment compares with the same bf16 centres, and the sums are order-free), so every later
+            # step would give the same centres, cost and labels — Spark's rule (moved <= tol) stops here
+            if tol == 0 and self._wfast and self.converged(0.0):
                 break
         return it
 

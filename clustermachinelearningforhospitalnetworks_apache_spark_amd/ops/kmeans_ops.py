@@ -141,6 +141,12 @@ _native.register_kernel_sigs({
     "cml_kmeans_centre_decay_stats": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp,
                                               c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cml_kmeans_mx_snap": (c_int, [c_vp, c_ll, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cml_kmeans_sort_perm": (c_int, [c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp]),
+    "cml_kmeans_wseg_slot_doubles": (c_ll, [c_int, c_int]),
+    "cml_kmeans_wseg_slot_ints": (c_ll, [c_int]),
+    "cml_kmeans_weighted_segsum": (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                                           c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
 })
 _native.register_host_sigs({
     "cml_local_kmeans_host": (c_int, [c_vp, c_int, c_int, c_vp, c_int, ctypes.c_uint64, ctypes.c_uint64, c_int,
@@ -637,6 +643,115 @@ def accumulate_sort(x: torch.Tensor, n: int, dp: int, d: int, labels: torch.Tens
     else:
         status = lib.cml_kmeans_sort_accum(*args, float(qscale), _native.stream_ptr(stream))
     _native.check(status, "kmeans_sort_accum")
+
+
+def sort_perm(labels: torch.Tensor, rank: torch.Tensor, hist: torch.Tensor, aplan: AssignPlan, n: int, k: int,
+              off: torch.Tensor, seg: torch.Tensor, perm: torch.Tensor, tail: torch.Tensor | None = None,
+              cost_part: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """The counting sort of ``accumulate_sort`` alone (no segmented sum): from the ``hist`` / ``rank`` an
+    ``assign_bf16`` under ``aplan`` produced, ``perm`` [>= n] = the row ids in label order and ``seg`` (
+    ``seg_buffer_ints(k)`` ints) with seg[c] = first sorted position of cluster c, seg[k] = n. Returns ``tail``
+    (f64 [k + 1]): the row count of every cluster, then Σ ``cost_part`` (0 without one)."""
+    i32 = torch.int32
+    if any(t.dtype != i32 or not t.is_contiguous() for t in (labels, rank, hist, off, seg, perm)):
+        raise ValueError("sort_perm: contiguous int32 labels, rank, hist, off, seg and perm")
+    if (labels.numel() < n or rank.numel() < n or perm.numel() < n or hist.numel() < aplan.grid * aplan.kp
+            or off.numel() < k * aplan.grid or seg.numel() < seg_buffer_ints(k) or k > aplan.kp):
+        raise ValueError("sort_perm: buffer lengths do not match n, k and the assign plan")
+    if tail is None:
+        tail = torch.empty(k + 1, dtype=torch.float64, device=labels.device)
+    elif tail.dtype != torch.float64 or tail.numel() < k + 1 or not tail.is_contiguous():
+        raise ValueError("sort_perm: tail is a contiguous f64 [k + 1] tensor")
+    if cost_part is not None and (cost_part.dtype != torch.float64 or cost_part.numel() < aplan.grid):
+        raise ValueError("sort_perm: cost_part is the assign's f64 [grid] tensor")
+    _native.check(_native.kernels().cml_kmeans_sort_perm(
+        int(n), labels.data_ptr(), rank.data_ptr(), hist.data_ptr(), aplan.grid, aplan.round_rows, int(k), aplan.kp,
+        _ptr(cost_part), aplan.grid, off.data_ptr(), seg.data_ptr(), perm.data_ptr(), tail.data_ptr(),
+        _native.stream_ptr(stream)), "kmeans_sort_perm")
+    return tail
+
+
+def wseg_slots(plan: AccumPlan, d: int, device) -> tuple:
+    """Scratch of ``weighted_sums``: per-slice head / tail partials (hi then lo) and their cluster ids."""
+    lib = _native.kernels()
+    sl = torch.empty(max(int(lib.cml_kmeans_wseg_slot_doubles(plan.seg_grid, d)), 1), dtype=torch.float64,
+                     device=device)
+    sc = torch.empty(max(int(lib.cml_kmeans_wseg_slot_ints(plan.seg_grid)), 1), dtype=torch.int32, device=device)
+    return sl, sc
+
+
+def _weighted_columns(x: torch.Tensor, n: int, d: int, w: torch.Tensor, xn64: torch.Tensor) -> torch.Tensor:
+    """[fl64(w·x) | w | fl64(w·xn64)] as f64 [n, d + 2]: what the weighted sums add, materialised (host twin)."""
+    xs = x[:n, :d]
+    x64 = (xs.to(torch.float32) if is_fp8(xs) else xs).to(torch.float64)
+    w = w[:n].to(torch.float64)
+    return torch.cat([x64 * w[:, None], w[:, None], (w * xn64[:n].to(torch.float64))[:, None]], 1)
+
+
+def weighted_sums(x: torch.Tensor, n: int, dp: int, d: int, w: torch.Tensor, xn64: torch.Tensor, k: int,
+                  perm: torch.Tensor, seg: torch.Tensor, plan: AccumPlan | None = None,
+                  out: tuple | None = None, slots: tuple | None = None, stream=None) -> tuple:
+    """K10w (``kmeans_weighted.hip``): per-cluster weighted sums of bf16 / e4m3 rows in the ``to_device_matrix``
+    layout, as normalised double-double ``(S, S_lo)``, each f64 [k, d + 2]: columns 0..d-1 Σ fl64(w_i·x_ij),
+    column d Σ w_i, column d+1 Σ fl64(w_i·xn64_i), over the rows of every cluster in the label-sorted order
+    ``perm`` / ``seg`` (``sort_perm``, or any permutation that groups the labels: the sums are the correctly
+    rounded exact sums of the rounded products, so the order does not change a bit while the products of a
+    column span fewer than ~106 - 53 - ceil(log2 n) binary orders). ``plan``: a sort-regime ``plan_accum``.
+    Host tensors take the host twin (``sums_reference`` on the materialised products)."""
+    if w.dtype != torch.float64 or xn64.dtype != torch.float64 or not w.is_contiguous() or not xn64.is_contiguous():
+        raise ValueError("weighted_sums: w and xn64 are contiguous f64 vectors")
+    if w.numel() < n or xn64.numel() < n or x.shape[0] < n:
+        raise ValueError("weighted_sums: w, xn64 and x need n rows")
+    if perm.dtype != torch.int32 or seg.dtype != torch.int32 or not perm.is_contiguous() or not seg.is_contiguous():
+        raise ValueError("weighted_sums: perm and seg are contiguous int32 tensors")
+    if perm.numel() < n or seg.numel() < k + 1:
+        raise ValueError("weighted_sums: perm [n] and seg [k + 1]")
+    if not x.is_cuda:
+        lab = torch.empty(n, dtype=torch.int64)
+        sizes = (seg[1:k + 1] - seg[:k]).long()
+        lab[perm[:n].long()] = torch.repeat_interleave(torch.arange(k), sizes)
+        S, _, S_lo = sums_reference(_weighted_columns(x, n, d, w, xn64), lab, k, with_lo=True)
+        return S, S_lo
+    fp8 = is_fp8(x)
+    if x.dtype != torch.bfloat16 and not fp8:
+        raise ValueError(f"weighted_sums: bf16 or e4m3 device rows, got {x.dtype}")
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < dp or not 0 < d <= dp or x.data_ptr() % 16 or (
+            x.stride(0) * x.element_size()) % 16:
+        raise ValueError("weighted_sums: rows in the to_device_matrix layout (16-byte aligned, padded width dp >= d)")
+    if plan is None:
+        plan = plan_accum(max(n, 1), dp, k, x.device.index or 0, force="sort", fp8=fp8)
+    if plan.mode != "sort" or 64 * plan.cpl < dp:
+        raise ValueError("weighted_sums: a sort-regime accumulation plan for this width")
+    f64 = dict(dtype=torch.float64, device=x.device)
+    S, S_lo = out if out is not None else (torch.empty((k, d + 2), **f64), torch.empty((k, d + 2), **f64))
+    if any(t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < k * (d + 2) for t in (S, S_lo)):
+        raise ValueError("weighted_sums: S and S_lo are contiguous f64 [k, d + 2] tensors")
+    sl, sc = slots if slots is not None else wseg_slots(plan, d, x.device)
+    _native.check(_native.kernels().cml_kmeans_weighted_segsum(
+        x.data_ptr(), int(n), x.stride(0), int(dp), int(d), int(fp8), w.data_ptr(), xn64.data_ptr(), perm.data_ptr(),
+        seg.data_ptr(), int(k), plan.cpl, plan.seg_grid, S.data_ptr(), S_lo.data_ptr(), sl.data_ptr(), sc.data_ptr(),
+        _native.stream_ptr(stream)), "kmeans_weighted_segsum")
+    return S, S_lo
+
+
+def weighted_sums_labels(x: torch.Tensor, n: int, dp: int, d: int, w: torch.Tensor, xn64: torch.Tensor,
+                         labels: torch.Tensor, k: int, plan: AccumPlan | None = None, stream=None) -> tuple:
+    """``weighted_sums`` from labels (tests, stand-alone use): ``perm`` / ``seg`` from a stable sort of the
+    labels and ``int_hist``. The same bits as the counting-sort front end: the sums do not depend on the order."""
+    if not x.is_cuda:
+        S, _, S_lo = sums_reference(_weighted_columns(x, n, d, w, xn64), labels[:n], k, with_lo=True)
+        return S, S_lo
+    lab = labels[:n]
+    lab = lab if lab.dtype == torch.int32 and lab.is_contiguous() else lab.to(torch.int32).contiguous()
+    counts = torch.zeros(k, dtype=torch.int32, device=x.device)
+    seg = torch.zeros(k + 1, dtype=torch.int32, device=x.device)
+    if n:
+        int_hist(lab, n, k, counts)
+        perm = torch.sort(lab, stable=True).indices.to(torch.int32)
+    else:
+        perm = torch.zeros(1, dtype=torch.int32, device=x.device)
+    seg[1:] = torch.cumsum(counts, 0, dtype=torch.int32)
+    return weighted_sums(x, n, dp, d, w, xn64, k, perm, seg, plan, stream=stream)
 
 
 class DeltaState:

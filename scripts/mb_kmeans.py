@@ -25,6 +25,10 @@ subcommand per experiment. The K9/K9r assign pass on its own is scripts/mb_k9r.p
         fp8 rows: MX-scaled fp8 MFMAs against the bf16 widening pass, one assign pass and pruned steps each way
     python scripts/mb_kmeans.py host [--rows 12500000] [--dim 256] [--k 256] [--iters 20] [--top 45]
         cProfile of the timed public-API fit after two warm-ups (scripts/sync_audit.py lists its blocking reads)
+    python scripts/mb_kmeans.py weighted [--rows 20000000] [--dim 256] [--k 256] [--dtype bf16|e4m3] [--source-rows 0]
+        weighted MFMA step, unweighted full step (prune / incremental off) and K10w alone, interleaved on the same
+        data, with K10w's bytes read over its time; --source-rows N also times 5-step weighted fits of the first N
+        rows on the bf16 and the source-precision paths
 """
 import argparse
 import cProfile
@@ -404,9 +408,64 @@ def cmd_host(argv):
         print("\n".join(line for line in s.getvalue().splitlines() if line.strip())[:20000])
 
 
+def cmd_weighted(argv):
+    a = parse("weighted", argv, rows=20_000_000, dim=256, k=256, dtype="bf16", reps=5, source_rows=0)
+    n, d, k = a.rows, a.dim, a.k
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = blobs(n, d, k, g)
+    if a.dtype == "e4m3":
+        x = (x.float() / 4).to(torch.float8_e4m3fn)
+    elif a.dtype != "bf16":
+        raise SystemExit("--dtype bf16 | e4m3")
+    w = torch.rand(n, device="cuda", generator=g, dtype=torch.float64) * 4
+    init = x[:k].float().double().cpu().numpy()
+    ew = LloydEngine(x, d, k, weights=w, precision="bf16")
+    eu = LloydEngine(x, d, k, prune=False, incremental=False, use_graph=False, precision="bf16")
+    for e in (ew, eu):
+        e.set_centers(init)
+        e.step()
+    torch.cuda.synchronize()
+    st = ew._wst
+
+    def k10w():
+        K.weighted_sums(ew.x, n, ew.dp, d, ew.w, ew._norms64(), k, ew.perm, ew.seg, ew.cplan, out=(st.S, st.S_lo),
+                        slots=st.slots)
+
+    # interleaved on the same data: weighted step, unweighted full step (same K9r pass, f64 kmeans_segacc), K10w alone
+    runs = {"weighted step": ew.step, "unweighted full step": eu.step, "K10w alone": k10w}
+    ts = {name: [] for name in runs}
+    for _ in range(a.reps):
+        for name, fn in runs.items():
+            ts[name] += event_list(fn, 1)
+    for name, v in ts.items():
+        v.sort()
+        print(f"{name}: best {v[0]:.3f} ms, median {v[len(v) // 2]:.3f} ms", flush=True)
+    by = n * (ew.dp * x.element_size() + 16 + 4)  # rows as stored + w + xn64 + perm
+    t = ts["K10w alone"][0]
+    print(f"n={n} d={d} (Dp {ew.dp}) k={k} {a.dtype} {ew.cplan}: K10w reads {by / 1e9:.2f} GB -> {by / 1e9 / t:.2f} TB/s; "
+          f"weighted / unweighted step = {ts['weighted step'][0] / ts['unweighted full step'][0]:.3f} (best), "
+          f"{ts['weighted step'][len(ts['weighted step']) // 2] / ts['unweighted full step'][len(ts['unweighted full step']) // 2]:.3f} (median)")
+    if a.source_rows:  # a size the source-precision weighted path still holds: both fits on the same data
+        m = min(n, a.source_rows)
+        xs, wsrc = x[:m], w[:m].contiguous()
+        for name, kw in (("bf16", dict(precision="bf16")), ("source precision", {})):
+            def fit():
+                e = LloydEngine(xs, d, k, weights=wsrc, **kw)
+                e.set_centers(init)
+                e.fit(5, 0.0)
+                return e.training_cost()
+            fit()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c = fit()
+            torch.cuda.synchronize()
+            print(f"weighted fit n={m} d={d} k={k}, 5 steps, {name}: {1e3 * (time.perf_counter() - t0):.1f} ms "
+                  f"(cost {c:.6g})", flush=True)
+
+
 COMMANDS = {"accum": cmd_accum, "segacc": cmd_segacc, "overlap": cmd_overlap, "rowpass": cmd_rowpass,
             "prune": cmd_prune, "bounds": cmd_bounds, "churn": cmd_churn, "graph": cmd_graph, "cert": cmd_cert,
-            "fp8-mx": cmd_fp8_mx, "host": cmd_host}
+            "fp8-mx": cmd_fp8_mx, "host": cmd_host, "weighted": cmd_weighted}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:
