@@ -22,6 +22,12 @@
         label_wsum, W / Q group sums) and the score pass (one MFMA pass over X) separately, best-of-5 ms; M is
         squaredEuclidean, cosine or both; --evaluate also times ClusteringEvaluator.evaluate end to end
 
+    python scripts/mb_ml.py bisecting [--rows 20000000] [--dim 256] [--k 8] [--max-iter 20] [--dtype bf16|fp8]
+                                      [--measure euclidean|cosine] [--weighted]
+        BisectingKMeans.fit end to end on blobs (seconds, ms per pass over the rows) and, where K27 takes the
+        column, the step kernel alone on all rows with and without the sums; CML_BISECT_KERNEL=0 times the
+        torch forms instead
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -407,7 +413,73 @@ def cmd_silhouette(argv):
                   f"silhouette {v:.6f}", flush=True)
 
 
-COMMANDS = {"silhouette": cmd_silhouette, "multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_bisecting(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.clustering import BisectingKMeans
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import bisect_ops as BO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import silhouette_ops as SO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    ap = argparse.ArgumentParser(prog="mb_ml.py bisecting")
+    ap.add_argument("--rows", type=int, default=20_000_000)
+    ap.add_argument("--dim", type=int, default=256)
+    ap.add_argument("--k", type=int, default=8)
+    ap.add_argument("--max-iter", type=int, default=20)
+    ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--measure", choices=["euclidean", "cosine"], default="euclidean")
+    ap.add_argument("--weighted", action="store_true")
+    a = ap.parse_args(argv)
+    n, d, k = a.rows, a.dim, a.k
+    dt = torch.float8_e4m3fn if a.dtype == "fp8" else torch.bfloat16
+    g = torch.Generator(device="cuda").manual_seed(1)
+    cen = torch.randn(k, d, generator=g, device="cuda") * 3.0
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # blobs in chunks: no n x d f32 temporary
+        t = torch.randint(0, k, (min(step, n - s0),), generator=g, device="cuda")
+        x[s0:s0 + step] = (cen[t] + torch.randn(len(t), d, generator=g, device="cuda")).to(torch.bfloat16)
+    xd = to_device_matrix(x.to(dt) if dt != torch.bfloat16 else x, d)
+    del x
+    cols = {"features": xd}
+    if a.weighted:
+        cols["w"] = torch.randint(0, 4, (n,), generator=g, device="cuda").to(torch.float64)
+    spark = SparkSession.builder.master("mi355x").getOrCreate()
+    df = spark.createDataFrameFromTensors(cols)
+    est = BisectingKMeans(k=k, seed=3, maxIter=a.max_iter, distanceMeasure=a.measure)
+    if a.weighted:
+        est = est.setWeightCol("w")
+    small = spark.createDataFrameFromTensors({c: v[:50_000] for c, v in cols.items()})
+    est.fit(small)  # loads the kernels
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    m = est.fit(df)
+    torch.cuda.synchronize()
+    fit_s = time.perf_counter() - t0
+
+    def levels(nd):
+        return 1 + max((levels(c) for c in nd.children), default=0)
+    nlev = levels(m._root) - 1
+    iters = nlev * (max(a.max_iter, 1) + 1) + 1  # per level: the iterations and the final assignment; the root
+    form = "K27" if BO.kernel_enabled() and BO.kernel_supported(xd.dtype, xd.shape[1]) else "torch"
+    print(f"bisecting {n}x{d} {a.dtype} k={k} maxIter={a.max_iter} {a.measure}{' weighted' if a.weighted else ''} "
+          f"[{form}]: fit {fit_s:.3f} s, {len(m.clusterCenters())} leaves on {nlev} levels, "
+          f"{1e3 * fit_s / iters:.2f} ms per pass ({iters} passes), trainingCost {m.trainingCost:.6e}", flush=True)
+    if form == "K27":  # the step alone: every row listed (level 1), two live children
+        cosine = a.measure == "cosine"
+        plan = BO.make_plan(torch.zeros(n, dtype=torch.int64, device="cuda"), 1)
+        c0 = torch.as_tensor(m._root.center, device="cuda")
+        ch = torch.zeros(1, 2, xd.shape[1], dtype=torch.float64, device="cuda")
+        ch[0, 0, :d], ch[0, 1, :d] = c0 * 0.999, c0 * 1.001
+        alive = torch.ones(1, 2, dtype=torch.bool, device="cuda")
+        w = cols.get("w")
+        nrm2 = SO.row_sqnorm(xd)
+        omega = (w if not cosine else (torch.reciprocal(nrm2.sqrt()) if w is None else w / nrm2.sqrt()))
+        for sums in (True, False):
+            ms = best_ms(lambda: BO.bisect_step(xd, plan, ch, alive, omega, w, None if cosine else nrm2, cosine, sums))
+            gb = xd.numel() * xd.element_size() / 1e9
+            print(f"  bisect_step want_sums={int(sums)}: {ms:.3f} ms, {gb / ms:.2f} TB/s rows", flush=True)
+
+
+COMMANDS = {"bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
