@@ -8,6 +8,10 @@ R_kᵀ·X and (R_k ∘ X)ᵀ·X as device GEMMs (hipBLASLt) — all k·(1 + d + 
 plus the log-likelihood go into ONE all-reduce per iteration. The M-step (k small d×d matrices)
 runs on the host in float64.
 
+bf16 / e4m3 device columns never become an f64 copy: their E-step is ``ops/gmm_ops.py`` (the K28 kernel for bf16
+rows of d <= 32, the chunked reference form otherwise), which returns the same all-reduced message; the M-step is
+shared. f32 / f64 columns and CPU frames keep the dense form above.
+
 Spark semantics: k=2, maxIter=100, tol=0.01 (stop when the log-likelihood improves by less than
 tol), init = means of k disjoint groups of ``nSamples`` = 5 rows sampled with replacement from the
 data (seeded) and the diagonal of the data variance as every initial covariance, uniform weights.
@@ -68,6 +72,50 @@ def _log_pdf(x: torch.Tensor, mus: np.ndarray, covs: np.ndarray) -> torch.Tensor
     return out
 
 
+def _inv_lower(L: np.ndarray) -> np.ndarray:
+    """L^-1 of a lower triangular matrix by forward substitution (exactly lower triangular)."""
+    d = L.shape[0]
+    A = np.zeros((d, d))
+    for i in range(d):
+        A[i, :i] = -(L[i, :i] @ A[:i, :i]) / L[i, i]
+        A[i, i] = 1.0 / L[i, i]
+    return A
+
+
+def _estep_tables(weights: np.ndarray, covs: np.ndarray):
+    """``(A [k, d, d], c [k])`` of ``ops/gmm_ops.py``: A_j = L_j^-1 and the constant of lp_j."""
+    d = covs.shape[1]
+    Ls = [_chol(cov) for cov in covs]
+    A = np.stack([_inv_lower(L) for L in Ls])
+    logdet = np.array([2.0 * float(np.log(np.diag(L)).sum()) for L in Ls])
+    return A, np.log(np.clip(weights, 1e-300, None)) - 0.5 * (d * _LOG2PI + logdet)
+
+
+def _low_precision(x: torch.Tensor) -> bool:
+    """bf16 and e4m3 device columns: the path without an f64 copy. Every other column keeps the dense form."""
+    return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
+
+
+def _use_kernel(x: torch.Tensor, k: int) -> bool:
+    from ..ops import gmm_ops as GO
+    from ..utils.device import padded_dim
+    return (x.dtype == torch.bfloat16 and GO.kernel_enabled()
+            and GO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), k))
+
+
+def _m_step(o: np.ndarray, k: int, d: int):
+    """``(weights, mus, covs, ll)`` from the all-reduced message [S0 | S1 | S2 | sum w lse | sum w]."""
+    s0 = o[:k]
+    s1 = o[k:k + k * d].reshape(k, d)
+    s2 = o[k + k * d:k + k * d + k * d * d].reshape(k, d, d)
+    ll, wt = float(o[-2]), float(o[-1])
+    s0c = np.clip(s0, 1e-300, None)
+    mus = s1 / s0c[:, None]
+    covs = s2 / s0c[:, None, None] - np.einsum("ki,kj->kij", mus, mus)
+    covs = 0.5 * (covs + np.transpose(covs, (0, 2, 1)))
+    return s0 / wt, mus, covs, ll
+
+
 class GaussianMixture(Estimator):
     _params = _GMM_PARAMS
 
@@ -76,7 +124,9 @@ class GaussianMixture(Estimator):
         for k in ("seed", "weightCol"):
             self._defaultParamMap.pop(k, None)
 
-    def _init(self, df, x: torch.Tensor, w: torch.Tensor, k: int, seed: int):
+    def _init(self, df, x: torch.Tensor, w, k: int, seed: int, lowp: bool = False):
+        """Initial (weights, means, covariances). ``lowp``: ``x`` is a bf16 / e4m3 device column and ``w`` may be
+        None; the sampled rows are widened after the gather and the variance comes from chunked sums."""
         comm = df._comm
         d = x.shape[1]
         n_samples = 5
@@ -88,16 +138,24 @@ class GaussianMixture(Estimator):
         picks = rng.integers(0, total, size=k * n_samples)  # global row ids, drawn order kept
         off = sum(counts[:comm.rank])
         pos = np.nonzero((picks >= off) & (picks < off + x.shape[0]))[0]
-        rows = x[torch.as_tensor(picks[pos] - off, dtype=torch.int64, device=x.device)].cpu().numpy()
+        idx = torch.as_tensor(picks[pos] - off, dtype=torch.int64, device=x.device)
+        if lowp:
+            from ..ops import gmm_ops as GO
+            rows = GO.gather_rows(x, idx, d).cpu().numpy()
+        else:
+            rows = x[idx].cpu().numpy()
         samp = np.zeros((k * n_samples, d))
         for p_, r_ in comm.allgather_object((pos, rows)):
             samp[p_] = r_
         mus = samp.reshape(k, n_samples, d).mean(1)
         # diagonal of the (weighted) data variance
-        W = w.sum()
-        s1 = (w[:, None] * x).sum(0)
-        s2 = (w[:, None] * x * x).sum(0)
-        msg = torch.cat([W.reshape(1), s1, s2])
+        if lowp:
+            msg = GO.column_moments(x, d, w)
+        else:
+            W = w.sum()
+            s1 = (w[:, None] * x).sum(0)
+            s2 = (w[:, None] * x * x).sum(0)
+            msg = torch.cat([W.reshape(1), s1, s2])
         comm.allreduce_(msg)
         o = msg.cpu().numpy()
         mean = o[1:1 + d] / o[0]
@@ -106,17 +164,23 @@ class GaussianMixture(Estimator):
         return np.full(k, 1.0 / k), mus, covs
 
     def _fit(self, df):
+        from .clustering import _weights
         from .tree_models import _default_seed
-        x = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
-        n, d = x.shape
+        x = df._feature_matrix(self.getFeaturesCol())
         k = self.getK()
         if k < 2:
             raise ValueError("GaussianMixture: k must be > 1")
-        w = df._column_data(self.getOrDefault("weightCol")).values.to(torch.float64) \
-            if self.isSet("weightCol") and self.getOrDefault("weightCol") else torch.ones(n, dtype=torch.float64,
-                                                                                         device=x.device)
+        # Spark's non-negative-weight check, agreed over the ranks before the first collective of the fit
+        w = _weights(df, self.getOrDefault("weightCol"), x.device) \
+            if self.isSet("weightCol") and self.getOrDefault("weightCol") else None
         seed = int(self.getOrDefault("seed")) if self.isSet("seed") else _default_seed(U.jvm_class(self))
         comm = df._comm
+        if _low_precision(x):
+            return self._fit_low_precision(df, x, w, k, seed)
+        x = x.to(torch.float64)
+        n, d = x.shape
+        if w is None:
+            w = torch.ones(n, dtype=torch.float64, device=x.device)
         weights, mus, covs = self._init(df, x, w, k, seed)
         ll_prev, ll = -np.inf, -np.inf
         it = 0
@@ -129,23 +193,40 @@ class GaussianMixture(Estimator):
             S2 = torch.stack([(R[:, j:j + 1] * x).T @ x for j in range(k)])
             msg = torch.cat([S0, S1.reshape(-1), S2.reshape(-1), (w * lse).sum().reshape(1), w.sum().reshape(1)])
             comm.allreduce_(msg)
-            o = msg.cpu().numpy()
-            s0 = o[:k]
-            s1 = o[k:k + k * d].reshape(k, d)
-            s2 = o[k + k * d:k + k * d + k * d * d].reshape(k, d, d)
-            ll, wt = float(o[-2]), float(o[-1])
-            s0c = np.clip(s0, 1e-300, None)
-            mus = s1 / s0c[:, None]
-            covs = s2 / s0c[:, None, None] - np.einsum("ki,kj->kij", mus, mus)
-            covs = 0.5 * (covs + np.transpose(covs, (0, 2, 1)))
-            weights = s0 / wt
+            weights, mus, covs, ll = _m_step(msg.cpu().numpy(), k, d)
             if abs(ll - ll_prev) < self.getTol():
                 break
             ll_prev = ll
+        return self._model(df, weights, mus, covs, ll, it)
+
+    def _model(self, df, weights, mus, covs, ll, it):
         model = GaussianMixtureModel(weights, mus, covs)
         self._copyValues(model)
         model._attach_summary(GaussianMixtureSummary(model, df, ll, it))
         return model
+
+    def _fit_low_precision(self, df, x: torch.Tensor, w: Optional[torch.Tensor], k: int, seed: int):
+        """bf16 / e4m3 device rows: the same EM with the E-step of ``ops/gmm_ops.py`` on the rows as they are."""
+        from ..ops import gmm_ops as GO
+        d = int(x.shape[1])
+        comm = df._comm
+        kernel = _use_kernel(x, k)
+        weights, mus, covs = self._init(df, x, w, k, seed, lowp=True)
+        if kernel:
+            from ..models.kmeans import to_device_matrix
+            x = to_device_matrix(x, d)  # a copy only when the layout is not already the kernel's
+        ll_prev, ll = -np.inf, -np.inf
+        it = 0
+        for it in range(1, self.getMaxIter() + 1):
+            A, c = _estep_tables(weights, covs)
+            stats, tail = (GO.estep if kernel else GO.estep_reference)(x, d, w, A, mus, c)
+            msg = torch.cat([stats[:, 0], stats[:, 1:1 + d].reshape(-1), stats[:, 1 + d:].reshape(-1), tail])
+            comm.allreduce_(msg)
+            weights, mus, covs, ll = _m_step(msg.cpu().numpy(), k, d)
+            if abs(ll - ll_prev) < self.getTol():
+                break
+            ll_prev = ll
+        return self._model(df, weights, mus, covs, ll, it)
 
 
 class GaussianMixtureModel(Model):
@@ -179,18 +260,33 @@ class GaussianMixtureModel(Model):
         from ..sql.session import SparkSession
         return SparkSession.builder.getOrCreate()
 
+    def _probs_labels(self, x: torch.Tensor):
+        """``(prob [n, k], label int32 [n])``; bf16 / e4m3 device rows go through ``ops/gmm_ops.py``."""
+        if not _low_precision(x):
+            p = self._probs(x)
+            return p, torch.argmax(p, 1).to(torch.int32)
+        from ..ops import gmm_ops as GO
+        d = int(x.shape[1])
+        A, c = _estep_tables(self._w, self._cov)
+        if _use_kernel(x, len(self._w)):
+            from ..models.kmeans import to_device_matrix
+            return GO.predict(to_device_matrix(x, d), d, A, self._mu, c)
+        return GO.predict_reference(x, d, None, A, self._mu, c)
+
     def _probs(self, x: torch.Tensor) -> torch.Tensor:
+        if _low_precision(x):
+            return self._probs_labels(x)[0]
         lp = _log_pdf(x.to(torch.float64), self._mu, self._cov) + torch.as_tensor(
             np.log(np.clip(self._w, 1e-300, None)), device=x.device)
         return torch.softmax(lp, 1)
 
     def _transform(self, df):
-        p = self._probs(df._feature_matrix(self.getFeaturesCol()))
+        p, lab = self._probs_labels(df._feature_matrix(self.getFeaturesCol()))
         out = df
         if self.getProbabilityCol():
             out = _replace_col(out, self.getProbabilityCol(), ColumnData(p.contiguous(), None, T.VectorUDT()))
         return _replace_col(out, self.getPredictionCol(),
-                            ColumnData(torch.argmax(p, 1).to(torch.int32), None, T.IntegerType()))
+                            ColumnData(lab, None, T.IntegerType()))
 
     def predict(self, value) -> int:
         from .linalg import as_array

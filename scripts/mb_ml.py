@@ -28,6 +28,11 @@
         column, the step kernel alone on all rows with and without the sums; CML_BISECT_KERNEL=0 times the
         torch forms instead
 
+    python scripts/mb_ml.py gmm [--rows 20000000] [--dim 32] [--k 8] [--max-iter 10] [--form kernel|reference|dense]
+        GaussianMixture.fit end to end on overlapping bf16 blobs (seconds, ms per EM iteration, peak allocation
+        rise) in one of three forms: the K28 kernel, the chunked reference form (CML_GMM_KERNEL=0), or the dense
+        f64 form on an f64 copy of the same values; for the kernel also estep and predict alone
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -479,7 +484,62 @@ def cmd_bisecting(argv):
             print(f"  bisect_step want_sums={int(sums)}: {ms:.3f} ms, {gb / ms:.2f} TB/s rows", flush=True)
 
 
-COMMANDS = {"bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_gmm(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml import gmm as G
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.clustering import GaussianMixture
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import gmm_ops as GO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    ap = argparse.ArgumentParser(prog="mb_ml.py gmm")
+    ap.add_argument("--rows", type=int, default=20_000_000)
+    ap.add_argument("--dim", type=int, default=32)
+    ap.add_argument("--k", type=int, default=8)
+    ap.add_argument("--max-iter", type=int, default=10)
+    ap.add_argument("--form", choices=["kernel", "reference", "dense"], default="kernel")
+    a = ap.parse_args(argv)
+    n, d, k = a.rows, a.dim, a.k
+    os.environ["CML_GMM_KERNEL"] = "1" if a.form == "kernel" else "0"
+    g = torch.Generator(device="cuda").manual_seed(1)
+    cen = torch.randn(k, d, generator=g, device="cuda") * 1.5
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # overlapping blobs in chunks: no n x d f32 temporary
+        t = torch.randint(0, k, (min(step, n - s0),), generator=g, device="cuda")
+        x[s0:s0 + step] = (cen[t] + torch.randn(len(t), d, generator=g, device="cuda")).to(torch.bfloat16)
+    xd = to_device_matrix(x, d)
+    del x
+    # dense: an f64 copy of the same values, the dense path's column (its conversion is not timed)
+    feats = xd[:, :d].to(torch.float64) if a.form == "dense" else xd
+    spark = SparkSession.builder.master("mi355x").getOrCreate()
+    df = spark.createDataFrameFromTensors({"features": feats})
+    est = GaussianMixture(k=k, seed=3, maxIter=a.max_iter, tol=0.0)
+    est.fit(spark.createDataFrameFromTensors({"features": feats[:50_000]}))  # loads the kernels
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    t0 = time.perf_counter()
+    m = est.fit(df)
+    torch.cuda.synchronize()
+    fit_s = time.perf_counter() - t0
+    rise = torch.cuda.max_memory_allocated() - base
+    xbytes = xd.numel() * xd.element_size()
+    its = m.summary.numIter
+    print(f"gmm {n}x{d} bf16 k={k} maxIter={a.max_iter} [{a.form}]: fit {fit_s:.3f} s, {its} iterations, "
+          f"{1e3 * fit_s / max(its, 1):.2f} ms per iteration, logLikelihood {m.summary.logLikelihood:.9e}, "
+          f"peak rise {rise / 2**20:.0f} MiB = {rise / xbytes:.2f} x the bf16 rows", flush=True)
+    if a.form == "kernel" and GO.kernel_supported(xd.dtype, xd.shape[1], k):
+        A, c = G._estep_tables(m._w, m._cov)
+        ms = best_ms(lambda: GO.estep(xd, d, None, A, m._mu, c))
+        dp = xd.shape[1]
+        flops = 2.0 * n * k * dp * dp * (0.75 if dp == 32 else 1.0) * 2  # MFMAs issued: both phases, lower blocks
+        print(f"  estep alone: {ms:.3f} ms, {flops / ms / 1e9:.1f} TF/s f64 issued "
+              f"({4.0 * n * k * d * d / ms / 1e9:.1f} TF/s of 4 n k d^2), {xbytes / ms / 1e9:.3f} TB/s rows",
+              flush=True)
+        ms = best_ms(lambda: GO.predict(xd, d, A, m._mu, c))
+        print(f"  predict alone: {ms:.3f} ms ({n * k * 8 / ms / 1e9:.2f} TB/s of prob written)", flush=True)
+
+
+COMMANDS = {"gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
