@@ -10,6 +10,11 @@ phinorm) are one more GEMM and are all-reduced across ranks with the log-p̂ ter
 document count in one message; λ and α updates (Spark's ``updateLambda`` / Newton ``updateAlpha``)
 are tiny and run identically on every rank.
 
+bf16 / e4m3 device columns never become an f64 copy: their E-step is ``ops/lda_ops.py`` (the K29 kernel for bf16
+rows inside its limits, the chunked reference form otherwise) on the list of the mini-batch's rows, which returns
+the same statistics for the same message; the λ and α updates are shared. f32 / f64 columns, CPU frames and the
+EM optimizer keep the dense form above.
+
 Randomness is counter-based (``utils.rng``: a hash of (seed, row id)) for the mini-batch
 Bernoulli draw and the per-document Gamma(100, 1/100) initial γ, so a fit is the same on any
 number of ranks; λ's Gamma(100, 1/100) init comes from a seeded generator shared by all ranks.
@@ -81,24 +86,58 @@ def _gamma_init(row_ids: torch.Tensor, k: int, seed: int) -> torch.Tensor:
     return torch.stack(cols, 1).to(torch.float64)
 
 
+def _low_precision(x: torch.Tensor) -> bool:
+    return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
+
+
+def _use_kernel(x: torch.Tensor, k: int) -> bool:
+    from ..ops import lda_ops as LO
+    from ..utils.device import padded_dim
+    return (x.dtype == torch.bfloat16 and LO.kernel_enabled()
+            and LO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), k))
+
+
+def _row_sums(X: torch.Tensor) -> torch.Tensor:
+    """f64 row sums; bf16 / e4m3 device rows are widened chunk by chunk."""
+    if _low_precision(X):
+        from ..ops import lda_ops as LO
+        return LO.row_sums(X, int(X.shape[1]))
+    return X.sum(1)
+
+
 def e_step(X: torch.Tensor, exp_elog_beta: torch.Tensor, alpha: torch.Tensor, gamma0: torch.Tensor):
     """Batched variational E-step: (γ [B, k], sstats [k, V], θ-expectations [B, k], phinorm [B, V]).
     A document stops updating once its mean |Δγ| <= 1e-3, exactly like Spark's per-document loop."""
+    return e_step_counted(X, exp_elog_beta, alpha, gamma0, count=False)[:4]
+
+
+def e_step_counted(X: torch.Tensor, exp_elog_beta: torch.Tensor, alpha: torch.Tensor, gamma0: torch.Tensor,
+                   count: bool = True, with_margin: bool = True):
+    """``e_step`` with, in addition, the sweeps every document ran (int32 [B]) and, with ``with_margin``, the
+    smallest ``|change - 1e-3|`` seen while a document was active (a 0-d tensor, else inf): how far the batch is
+    from a document whose stopping sweep another summation order could move."""
     gamma = gamma0.clone()
     e_theta = torch.exp(dirichlet_expectation(gamma))
     phinorm = e_theta @ exp_elog_beta + 1e-100
     active = torch.ones(X.shape[0], dtype=torch.bool, device=X.device)
+    sweeps = torch.zeros(X.shape[0], dtype=torch.int32, device=X.device)
+    margin = torch.full((), float("inf"), dtype=torch.float64, device=X.device)
     for _ in range(_E_MAX_SWEEPS):
         new_gamma = e_theta * ((X / phinorm) @ exp_elog_beta.T) + alpha[None, :]
         change = (new_gamma - gamma).abs().mean(1)
         gamma = torch.where(active[:, None], new_gamma, gamma)
         e_theta = torch.where(active[:, None], torch.exp(dirichlet_expectation(gamma)), e_theta)
         phinorm = e_theta @ exp_elog_beta + 1e-100
+        if count and X.shape[0]:
+            sweeps += active
+            if with_margin:
+                gap = torch.where(active, (change - _E_TOL).abs(), torch.full_like(change, float("inf")))
+                margin = torch.minimum(margin, gap.min())
         active = active & (change > _E_TOL)
         if not bool(active.any()):
             break
     sstats = e_theta.T @ (X / phinorm)
-    return gamma, sstats, e_theta, phinorm
+    return gamma, sstats, e_theta, phinorm, sweeps, margin
 
 
 class LDA(Estimator):
@@ -125,7 +164,10 @@ class LDA(Estimator):
         if k < 2:
             raise ValueError("LDA: k must be > 1")
         comm = df._comm
-        X = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
+        X = df._feature_matrix(self.getFeaturesCol())
+        if _low_precision(X):
+            return self._fit_low_precision(df, X, k)
+        X = X.to(torch.float64)
         ids = df._row_ids
         nonempty = X.sum(1) > 0
         X, ids = X[nonempty], ids[nonempty]
@@ -153,6 +195,55 @@ class LDA(Estimator):
                 stat += ss
                 logphat += dirichlet_expectation(g).sum(0)
             msg = torch.cat([stat.reshape(-1), logphat, torch.tensor([float(Xb.shape[0])], dtype=torch.float64,
+                                                                     device=dev)])
+            comm.allreduce_(msg)
+            nb = float(msg[-1])
+            if nb == 0:
+                continue
+            stat = msg[:k * V].reshape(k, V)
+            logphat = msg[k * V:k * V + k]
+            rho = (tau0 + it) ** (-kappa)
+            lam = (1.0 - rho) * lam + rho * (eta + stat * e_beta * (corpus / nb))
+            if self.getOptimizeDocConcentration():
+                alpha = _update_alpha(alpha, logphat / nb, nb, rho)
+        model = LocalLDAModel(lam.T.cpu().numpy(), alpha.cpu().numpy(), eta, V)
+        self._copyValues(model)
+        model._gamma_seed = seed
+        return model
+
+    def _fit_low_precision(self, df, x: torch.Tensor, k: int):
+        """bf16 / e4m3 device rows: the same online fit with the E-step of ``ops/lda_ops.py`` on the rows as
+        they are (no f64 copy of the column, no copy of the mini-batch): per iteration the list of picked
+        non-empty rows, one E-step call, and the same message."""
+        from ..ops import lda_ops as LO
+        comm = df._comm
+        V = int(x.shape[1])
+        dev = x.device
+        ids = df._row_ids
+        nonempty = LO.row_sums(x, V) > 0
+        seed = self._seed()
+        alpha = self._alpha0(k).to(dev)
+        eta = self.getOrDefault("topicConcentration") if self.isSet("topicConcentration") else None
+        eta = 1.0 / k if eta is None or eta < 0 else float(eta)
+        cnt = torch.tensor([float(df._nrows)], dtype=torch.float64, device=dev)
+        comm.allreduce_(cnt)
+        corpus = float(cnt[0])
+        gen = np.random.default_rng(seed & 0xFFFFFFFF)
+        lam = torch.as_tensor(gen.gamma(GAMMA_SHAPE, 1.0 / GAMMA_SHAPE, size=(k, V)), device=dev)
+        tau0, kappa, frac = self.getLearningOffset(), self.getLearningDecay(), self.getSubsamplingRate()
+        kernel = _use_kernel(x, k)
+        if kernel:
+            from ..models.kmeans import to_device_matrix
+            x = to_device_matrix(x, V)  # a copy only when the layout is not already the kernel's
+        for it in range(1, self.getMaxIter() + 1):
+            e_beta = torch.exp(dirichlet_expectation(lam))
+            rows = torch.nonzero(nonempty & (R.uniform(ids, seed, 1_000_003 + it) < frac)).reshape(-1)
+            gamma0 = _gamma_init(ids[rows], k, seed)
+            if kernel:
+                _, stat, logphat, _ = LO.estep(x, rows, V, e_beta, alpha, gamma0)
+            else:
+                _, stat, logphat, _ = LO.estep_reference(x, rows, V, e_beta, alpha, gamma0)
+            msg = torch.cat([stat.reshape(-1), logphat, torch.tensor([float(rows.shape[0])], dtype=torch.float64,
                                                                      device=dev)])
             comm.allreduce_(msg)
             nb = float(msg[-1])
@@ -286,12 +377,27 @@ class LocalLDAModel(Model):
         return rows_round_robin(SparkSession.builder.getOrCreate(), schema, rows)
 
     def _infer(self, df):
-        X = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
+        """``(X, gamma, lambda, alpha)``. bf16 / e4m3 device rows stay as they are (``X`` is the column itself) and
+        take gamma from ``ops/lda_ops.py``; every other column is widened to f64 and runs ``e_step``."""
+        X = df._feature_matrix(self.getFeaturesCol())
+        lowp = _low_precision(X)
+        if not lowp:
+            X = X.to(torch.float64)
         dev = X.device
         lam = torch.as_tensor(self._topics.T, device=dev)
         e_beta = torch.exp(dirichlet_expectation(lam))
         alpha = torch.as_tensor(self._alpha, device=dev)
         k = lam.shape[0]
+        if lowp:
+            from ..ops import lda_ops as LO
+            V = int(X.shape[1])
+            gamma0 = _gamma_init(df._row_ids, k, self._gamma_seed)
+            if _use_kernel(X, k):
+                from ..models.kmeans import to_device_matrix
+                gammas, _ = LO.infer(to_device_matrix(X, V), None, V, e_beta, alpha, gamma0)
+            else:
+                gammas = LO.estep_reference(X, None, V, e_beta, alpha, gamma0)[0]
+            return X, gammas, lam, alpha
         gammas = torch.zeros((X.shape[0], k), dtype=torch.float64, device=dev)
         lse_part = torch.zeros(X.shape[0], dtype=torch.float64, device=dev)
         for a in range(0, X.shape[0], _CHUNK):
@@ -302,7 +408,7 @@ class LocalLDAModel(Model):
 
     def _transform(self, df):
         X, g, _, _ = self._infer(df)
-        empty = X.sum(1) == 0
+        empty = _row_sums(X) == 0
         dist = g / g.sum(1, keepdim=True)
         dist = torch.where(empty[:, None], torch.zeros_like(dist), dist)
         return _replace_col(df, self.getTopicDistributionCol(), ColumnData(dist.contiguous(), None, T.VectorUDT()))
@@ -310,16 +416,23 @@ class LocalLDAModel(Model):
     def logLikelihood(self, dataset) -> float:
         """Variational lower bound on log p(corpus) (Spark's LDAModel.logLikelihood)."""
         X, g, lam, alpha = self._infer(dataset)
-        nonempty = X.sum(1) > 0
-        X, g = X[nonempty], g[nonempty]
+        lowp = _low_precision(X)
+        nonempty = _row_sums(X) > 0
+        if lowp:  # the rows are widened chunk by chunk below
+            from ..ops import lda_ops as LO
+            idx = torch.nonzero(nonempty).reshape(-1)
+            g = g[nonempty]
+        else:
+            X, g = X[nonempty], g[nonempty]
         elog_theta = dirichlet_expectation(g)
         elog_beta = dirichlet_expectation(lam)
         # Σ_w c_w log Σ_k exp(E[log θ_k] + E[log β_kw]), via a stable logsumexp over k
         doc = torch.zeros((), dtype=torch.float64, device=X.device)
         step = max(1, (1 << 24) // max(1, lam.shape[0] * lam.shape[1]))  # bound the [B, k, V] temporary
-        for a in range(0, X.shape[0], step):
+        for a in range(0, g.shape[0], step):
             t = torch.logsumexp(elog_theta[a:a + step, :, None] + elog_beta[None, :, :], 1)
-            doc = doc + (X[a:a + step] * t).sum()
+            xc = LO.gather_rows(X, idx[a:a + step], lam.shape[1]) if lowp else X[a:a + step]
+            doc = doc + (xc * t).sum()
         doc = doc + ((alpha[None, :] - g) * elog_theta).sum() + (torch.lgamma(g) - torch.lgamma(alpha)[None, :]).sum()
         doc = doc + (torch.lgamma(alpha.sum()) - torch.lgamma(g.sum(1))).sum()
         msg = doc.reshape(1).clone()
@@ -331,8 +444,8 @@ class LocalLDAModel(Model):
         return float(msg[0] + topics)
 
     def logPerplexity(self, dataset) -> float:
-        X = dataset._feature_matrix(self.getFeaturesCol()).to(torch.float64)
-        tok = X.sum().reshape(1).clone()
+        X = dataset._feature_matrix(self.getFeaturesCol())
+        tok = (_row_sums(X).sum() if _low_precision(X) else X.to(torch.float64).sum()).reshape(1).clone()
         dataset._comm.allreduce_(tok)
         return -self.logLikelihood(dataset) / float(tok[0])
 

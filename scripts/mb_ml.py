@@ -33,6 +33,13 @@
         rise) in one of three forms: the K28 kernel, the chunked reference form (CML_GMM_KERNEL=0), or the dense
         f64 form on an f64 copy of the same values; for the kernel also estep and predict alone
 
+    python scripts/mb_ml.py lda [--rows 4000000] [--terms 256] [--k 10] [--subsampling 0.05] [--max-iter 10]
+                                [--length 100] [--form kernel|reference|dense]
+        LDA.fit (online optimizer) end to end on a planted-topic bf16 corpus (seconds, ms per iteration, peak
+        allocation rise) in one of three forms: the K29 kernel, the chunked reference form (CML_LDA_KERNEL=0), or
+        the dense f64 form on an f64 copy of the same values; for the kernel also the E-step alone on one
+        mini-batch with its issued f64 MFMA rate, and the sweep histogram of that mini-batch
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -539,7 +546,88 @@ def cmd_gmm(argv):
         print(f"  predict alone: {ms:.3f} ms ({n * k * 8 / ms / 1e9:.2f} TB/s of prob written)", flush=True)
 
 
-COMMANDS = {"gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_lda(argv):
+    import numpy as np
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml import lda as L
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.clustering import LDA
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import lda_ops as LO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.utils import rng as R
+    ap = argparse.ArgumentParser(prog="mb_ml.py lda")
+    ap.add_argument("--rows", type=int, default=4_000_000)
+    ap.add_argument("--terms", type=int, default=256)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--subsampling", type=float, default=0.05)
+    ap.add_argument("--max-iter", type=int, default=10)
+    ap.add_argument("--length", type=float, default=100.0, help="mean tokens per document")
+    ap.add_argument("--form", choices=["kernel", "reference", "dense"], default="kernel")
+    a = ap.parse_args(argv)
+    n, V, k = a.rows, a.terms, a.k
+    os.environ["CML_LDA_KERNEL"] = "1" if a.form == "kernel" else "0"
+    g = torch.Generator(device="cuda").manual_seed(1)
+    # planted topics ~ Dirichlet(0.1), document mixtures ~ Dirichlet(0.3) (normalised Gamma draws); the counts
+    # of a document are Poisson(length * p_w), in chunks: no n x V f32 temporary
+    conc = torch.distributions.Gamma(torch.tensor(0.1, device="cuda"), torch.tensor(1.0, device="cuda"))
+    torch.manual_seed(1)
+    topics = conc.sample((k, V)) + 1e-30
+    topics = topics / topics.sum(1, keepdim=True)
+    mixc = torch.distributions.Gamma(torch.tensor(0.3, device="cuda"), torch.tensor(1.0, device="cuda"))
+    x = torch.empty(n, V, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 20
+    for s0 in range(0, n, step):
+        m = min(step, n - s0)
+        th = mixc.sample((m, k)) + 1e-30
+        p = (th / th.sum(1, keepdim=True)) @ topics
+        x[s0:s0 + m] = torch.poisson(p * a.length, generator=g).clamp(max=256.0).to(torch.bfloat16)
+    xd = to_device_matrix(x, V)
+    del x
+    # dense: an f64 copy of the same values, the dense path's column (its conversion is not timed)
+    feats = xd[:, :V].to(torch.float64) if a.form == "dense" else xd
+    spark = SparkSession.builder.master("mi355x").getOrCreate()
+    df = spark.createDataFrameFromTensors({"features": feats})
+    est = LDA(k=k, seed=3, maxIter=a.max_iter, subsamplingRate=a.subsampling)
+    est.fit(spark.createDataFrameFromTensors({"features": feats[:50_000]}))  # loads the kernels
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    t0 = time.perf_counter()
+    m = est.fit(df)
+    torch.cuda.synchronize()
+    fit_s = time.perf_counter() - t0
+    rise = torch.cuda.max_memory_allocated() - base
+    xbytes = xd.numel() * xd.element_size()
+    print(f"lda {n}x{V} bf16 k={k} subsampling={a.subsampling} maxIter={a.max_iter} [{a.form}]: fit {fit_s:.3f} s, "
+          f"{1e3 * fit_s / max(a.max_iter, 1):.2f} ms per iteration, alpha[0] {m.estimatedDocConcentration()[0]:.9e}, "
+          f"peak rise {rise / 2**20:.0f} MiB = {rise / xbytes:.2f} x the bf16 rows", flush=True)
+    dp = xd.shape[1]
+    if a.form == "kernel" and LO.kernel_supported(xd.dtype, dp, k):
+        # the E-step alone on the last iteration's mini-batch with the fitted topics
+        ids = df._row_ids
+        rows = torch.nonzero((LO.row_sums(xd, V) > 0) & (R.uniform(ids, 3, 1_000_003 + a.max_iter) < a.subsampling))
+        rows = rows.reshape(-1)
+        lam = torch.as_tensor(m._topics.T, device="cuda")
+        e_beta = torch.exp(L.dirichlet_expectation(lam))
+        alpha = torch.as_tensor(m._alpha, device="cuda")
+        g0 = L._gamma_init(ids[rows], k, 3)
+        out = []
+        ms = best_ms(lambda: out.append(LO.estep(xd, rows, V, e_beta, alpha, g0)), reps=3)
+        sw = out[-1][3].to(torch.float64)
+        nb = int(rows.shape[0])
+        pad = (-nb) % 16
+        grp = torch.cat([sw, torch.zeros(pad, dtype=sw.dtype, device=sw.device)]).reshape(-1, 16).max(1).values
+        kp = 16 if k <= 16 else 32
+        per_block = (kp // 2) * 2048.0  # f64 flops of the MFMAs issued per 16 documents x 16 terms, either phase
+        flops = (float(grp.sum()) + 4.0 * ((nb + 63) // 64)) * (dp // 16) * per_block
+        q = np.percentile(sw.cpu().numpy(), [0, 50, 99, 100])
+        print(f"  estep alone on {nb} documents: {ms:.3f} ms, {flops / ms / 1e9:.2f} TF/s f64 MFMA issued, "
+              f"{nb * dp * 2 / ms / 1e9:.4f} TB/s rows", flush=True)
+        print(f"  sweeps min / median / p99 / max = {q[0]:.0f} / {q[1]:.0f} / {q[2]:.0f} / {q[3]:.0f}, mean "
+              f"{float(sw.mean()):.1f}; mean over 16-document groups of the group's maximum / mean sweeps = "
+              f"{float(grp.mean()) / float(sw.mean()):.2f}", flush=True)
+
+
+COMMANDS = {"lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
