@@ -13,7 +13,9 @@ MI355X-first:
   topology); the full-batch loss and gradient of the flat weight vector come from device GEMMs
   (hipBLASLt) with autograd, all-reduced, and fed to the same L-BFGS (solver 'l-bfgs') or to plain
   gradient descent (solver 'gd'). Weight layout = Spark's: per layer W (out x in, column-major)
-  then b.
+  then b. bf16 / e4m3 device columns never become an f64 copy: their loss, gradient and scores come
+  from ``ops/mlp_ops.py`` (the K30 kernel for bf16 rows inside its limits, the chunked reference
+  form otherwise), which returns the same all-reduced message.
 """
 from __future__ import annotations
 
@@ -374,6 +376,18 @@ def _mlp_size(layers: List[int]) -> int:
     return sum(a * b + b for a, b in zip(layers[:-1], layers[1:]))
 
 
+def _low_precision(x: torch.Tensor) -> bool:
+    """bf16 and e4m3 device columns: the path without an f64 copy. Every other column keeps the dense form."""
+    return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
+
+
+def _use_kernel(x: torch.Tensor, layers: List[int]) -> bool:
+    from ..ops import mlp_ops as MO
+    from ..utils.device import padded_dim
+    return (x.dtype == torch.bfloat16 and MO.kernel_enabled()
+            and MO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), layers))
+
+
 class MultilayerPerceptronClassifier(Estimator):
     """Feed-forward network: sigmoid hidden layers, softmax output with cross-entropy loss, trained
     full-batch (L-BFGS or gradient descent); weights initialised uniformly in ±sqrt(6/(in+out))
@@ -390,10 +404,13 @@ class MultilayerPerceptronClassifier(Estimator):
         layers = [int(v) for v in self.getLayers()]
         if len(layers) < 2:
             raise ValueError("MultilayerPerceptronClassifier: layers needs an input and an output size")
-        x = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
+        x = df._feature_matrix(self.getFeaturesCol())
+        lowp = _low_precision(x)
+        if not lowp:
+            x = x.to(torch.float64)
         if x.shape[1] != layers[0]:
             raise ValueError(f"MultilayerPerceptronClassifier: input layer {layers[0]} != feature size {x.shape[1]}")
-        y = df._column_data(self.getLabelCol()).values.to(torch.int64)
+        y = df._column_data(self.getLabelCol()).values.to(torch.int32 if lowp else torch.int64)
         comm = df._comm
         k = layers[-1]
         if y.numel() and (int(y.max()) >= k or int(y.min()) < 0):
@@ -413,18 +430,34 @@ class MultilayerPerceptronClassifier(Estimator):
                 lim = np.sqrt(6.0 / (a + b))
                 parts += [rng.uniform(-lim, lim, a * b), rng.uniform(-lim, lim, b)]
             p0 = np.concatenate(parts)
-        Y = torch.nn.functional.one_hot(y, k).to(torch.float64) if y.numel() else torch.zeros(
-            (0, k), dtype=torch.float64, device=x.device)
+        if lowp:
+            # the rows as they are: K30 on bf16 rows inside its limits, the chunked reference form otherwise
+            from ..ops import mlp_ops as MO
+            kernel = _use_kernel(x, layers)
+            if kernel:
+                from ..models.kmeans import to_device_matrix
+                x = to_device_matrix(x, layers[0])  # a copy only when the layout is not already the kernel's
+            y = y.contiguous()
 
-        def fg(p):
-            pt = torch.as_tensor(p, device=x.device).requires_grad_(True)
-            z = _mlp_forward(x, _mlp_unpack(pt, layers))
-            loss = (torch.logsumexp(z, 1) - (z * Y).sum(1)).sum()
-            g, = torch.autograd.grad(loss, pt)
-            msg = torch.cat([g.detach(), loss.detach().reshape(1)])
-            comm.allreduce_(msg)
-            o = msg.cpu().numpy()
-            return float(o[-1]) / N, o[:-1] / N
+            def fg(p):
+                pt = torch.as_tensor(p, device=x.device)
+                msg = (MO.loss_grad if kernel else MO.loss_grad_reference)(x, layers[0], y, layers, pt)
+                comm.allreduce_(msg)
+                o = msg.cpu().numpy()
+                return float(o[-1]) / N, o[:-1] / N
+        else:
+            Y = torch.nn.functional.one_hot(y, k).to(torch.float64) if y.numel() else torch.zeros(
+                (0, k), dtype=torch.float64, device=x.device)
+
+            def fg(p):
+                pt = torch.as_tensor(p, device=x.device).requires_grad_(True)
+                z = _mlp_forward(x, _mlp_unpack(pt, layers))
+                loss = (torch.logsumexp(z, 1) - (z * Y).sum(1)).sum()
+                g, = torch.autograd.grad(loss, pt)
+                msg = torch.cat([g.detach(), loss.detach().reshape(1)])
+                comm.allreduce_(msg)
+                o = msg.cpu().numpy()
+                return float(o[-1]) / N, o[:-1] / N
 
         if self.getSolver() == "l-bfgs":
             p, hist, iters = lbfgs(fg, p0, self.getMaxIter(), self.getTol())
@@ -478,6 +511,16 @@ class MultilayerPerceptronClassificationModel(Model):
 
     def _scores(self, x: torch.Tensor) -> torch.Tensor:
         p = torch.as_tensor(self._w, device=x.device)
+        if _low_precision(x):  # no f64 copy of the rows: ops/mlp_ops.py
+            from ..ops import mlp_ops as MO
+            d = int(x.shape[1])
+            if d != self._layers[0]:
+                raise ValueError(f"MultilayerPerceptronClassificationModel: input layer {self._layers[0]} != "
+                                 f"feature size {d}")
+            if _use_kernel(x, self._layers):
+                from ..models.kmeans import to_device_matrix
+                return MO.forward(to_device_matrix(x, d), d, self._layers, p)
+            return MO.forward_reference(x, d, self._layers, p)
         return _mlp_forward(x.to(torch.float64), _mlp_unpack(p, self._layers))
 
     def _transform(self, df):

@@ -40,6 +40,13 @@
         the dense f64 form on an f64 copy of the same values; for the kernel also the E-step alone on one
         mini-batch with its issued f64 MFMA rate, and the sweep histogram of that mini-batch
 
+    python scripts/mb_ml.py mlp [--rows 20000000] [--layers 64,16,4] [--max-iter 10] [--form kernel|reference|dense]
+                                [--pass-only]
+        MultilayerPerceptronClassifier.fit end to end on bf16 rows labelled by a noisy linear rule (seconds, ms
+        per loss + gradient evaluation, peak allocation rise) in one of three forms: the K30 kernel, the chunked
+        reference form (CML_MLP_KERNEL=0), or the dense autograd form on an f64 copy of the same values; for the
+        kernel also loss_grad and forward alone with the issued f64 MFMA rate. --pass-only skips the fit
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -627,7 +634,86 @@ def cmd_lda(argv):
               f"{float(grp.mean()) / float(sw.mean()):.2f}", flush=True)
 
 
-COMMANDS = {"lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_mlp(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.classification_more import (
+        MultilayerPerceptronClassifier)
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import mlp_ops as MO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    ap = argparse.ArgumentParser(prog="mb_ml.py mlp")
+    ap.add_argument("--rows", type=int, default=20_000_000)
+    ap.add_argument("--layers", default="64,16,4")
+    ap.add_argument("--max-iter", type=int, default=10)
+    ap.add_argument("--form", choices=["kernel", "reference", "dense"], default="kernel")
+    ap.add_argument("--pass-only", action="store_true", help="no fit: one loss + gradient pass of the kernel")
+    a = ap.parse_args(argv)
+    layers = [int(v) for v in a.layers.split(",")]
+    n, d, C = a.rows, layers[0], layers[-1]
+    os.environ["CML_MLP_KERNEL"] = "1" if a.form == "kernel" else "0"
+    g = torch.Generator(device="cuda").manual_seed(1)
+    w = torch.randn(d, C, generator=g, device="cuda")
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    y = torch.empty(n, dtype=torch.float64, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # a planted linear rule with noise, in chunks: no n x d f32 temporary
+        v = torch.randn(min(step, n - s0), d, generator=g, device="cuda")
+        x[s0:s0 + step] = v.to(torch.bfloat16)
+        y[s0:s0 + step] = torch.argmax(v @ w + 0.5 * torch.randn(len(v), C, generator=g, device="cuda"), 1)
+        del v
+    xd = to_device_matrix(x, d)
+    del x
+    xbytes = xd.numel() * xd.element_size()
+
+    def kernel_alone(p):
+        y32 = y.to(torch.int32)
+        ms = best_ms(lambda: MO.loss_grad(xd, d, y32, layers, p))
+        nl, t = len(layers) - 1, 1 if max(layers[1:]) <= 16 else 2
+        # MFMAs issued per 64-row tile: layer 1 forward and dW_1 16 t dp/16 each; per upper layer the forward
+        # and backward 16 t^2 each and the 16 of each of its t^2 gradient blocks
+        flops = ((n + 63) // 64) * (2 * 16 * t * (xd.shape[1] // 16) + (nl - 1) * 48 * t * t) * 2048.0
+        print(f"  loss_grad alone at {n}x{d} {layers}: {ms:.3f} ms, {flops / ms / 1e9:.2f} TF/s f64 MFMA issued, "
+              f"{xbytes / ms / 1e9:.3f} TB/s rows", flush=True)
+        ms = best_ms(lambda: MO.forward(xd, d, layers, p))
+        print(f"  forward alone: {ms:.3f} ms ({n * C * 8 / ms / 1e9:.2f} TB/s of scores written)", flush=True)
+
+    if a.pass_only:
+        import numpy as np
+        rs = np.random.RandomState(3)
+        kernel_alone(torch.as_tensor(np.concatenate([rs.uniform(-1, 1, i * o + o) * np.sqrt(6.0 / (i + o))
+                                                     for i, o in zip(layers[:-1], layers[1:])]), device="cuda"))
+        return
+    # dense: an f64 copy of the same values, the dense path's column (its conversion is not timed)
+    feats = xd[:, :d].to(torch.float64) if a.form == "dense" else xd
+    spark = SparkSession.builder.master("mi355x").getOrCreate()
+    df = spark.createDataFrameFromTensors({"features": feats, "label": y})
+    est = MultilayerPerceptronClassifier(layers=layers, seed=3, maxIter=a.max_iter, tol=0.0)
+    est.fit(spark.createDataFrameFromTensors({"features": feats[:50_000], "label": y[:50_000]}))  # loads the kernels
+    evals = []
+    real, real_ref = MO.loss_grad, MO.loss_grad_reference
+    MO.loss_grad = lambda *aa, **kk: (evals.append(1), real(*aa, **kk))[1]
+    MO.loss_grad_reference = lambda *aa, **kk: (evals.append(1), real_ref(*aa, **kk))[1]
+    real_grad = torch.autograd.grad  # the dense form's evaluations
+    torch.autograd.grad = lambda *aa, **kk: (evals.append(1), real_grad(*aa, **kk))[1]
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    t0 = time.perf_counter()
+    m = est.fit(df)
+    torch.cuda.synchronize()
+    fit_s = time.perf_counter() - t0
+    MO.loss_grad, MO.loss_grad_reference, torch.autograd.grad = real, real_ref, real_grad
+    rise = torch.cuda.max_memory_allocated() - base
+    hist = m.summary.objectiveHistory
+    ne = len(evals) if evals else None
+    per = f", {ne} evaluations, {1e3 * fit_s / ne:.2f} ms per evaluation" if ne else ""
+    print(f"mlp {n}x{d} bf16 layers={layers} maxIter={a.max_iter} [{a.form}]: fit {fit_s:.3f} s, "
+          f"{m.summary.totalIterations} iterations{per}, final loss {hist[-1]:.12e}, peak rise {rise / 2**20:.0f} MiB = {rise / xbytes:.2f} x the bf16 rows",
+          flush=True)
+    if a.form == "kernel" and MO.kernel_supported(xd.dtype, xd.shape[1], layers):
+        kernel_alone(torch.as_tensor(m.weights.toArray(), device="cuda"))
+
+
+COMMANDS = {"mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
