@@ -11,9 +11,10 @@ decorrelating the feature vector).  Design, MI355X-first:
   gathered once, sorted on the device), splits = distinct quantiles at
   ``[0, 1/B, ..., 1]`` with ±inf at the ends, as Spark's ``approxQuantile`` at
   relativeError 0 would give; returns a Bucketizer (as Spark does).
-* PCA.fit: covariance from the K15 Gram kernel (``[X 1 0]ᵀ[X 1 0]`` in float64,
-  one all-reduce of (d+2)² doubles), eigen-decomposition on the host; ``transform``
-  projects without centring (Spark's ``PCAModel.transform``).
+* PCA.fit: covariance from the Gram kernels (K15 up to 30 columns, K31 for wider bf16
+  columns; ``[X 1 0]ᵀ[X 1 0]`` in float64, one all-reduce of (d+2)² doubles),
+  eigen-decomposition on the host; ``transform`` projects without centring (Spark's
+  ``PCAModel.transform``), a device column chunk by chunk without an f64 copy of it.
 """
 from __future__ import annotations
 
@@ -30,6 +31,8 @@ from .base import Estimator, Model, Transformer
 from .colutil import _auto_output, _replace_col
 from .linalg import DenseMatrix, DenseVector
 from .param import NO_DEFAULT
+
+_TRANSFORM_CHUNK = 8192  # rows of a device column that PCAModel.transform widens to f64 at a time
 
 
 class Bucketizer(Transformer):
@@ -157,7 +160,7 @@ class PCA(Estimator):
         if not 0 < k <= d:
             raise ValueError(f"PCA: k={k} must be in [1, {d}]")
         zero = torch.zeros(x.shape[0], dtype=torch.float64, device=x.device)
-        G = glm_ops.gram(x, d, zero)  # K15: [X 1 0]ᵀ[X 1 0]
+        G = glm_ops.gram(x, d, zero)  # K15 (d <= 30) / K31 (bf16, d <= 512): [X 1 0]ᵀ[X 1 0]
         df._comm.allreduce_(G)
         g = G.cpu().numpy()
         n = g[d, d]
@@ -196,9 +199,18 @@ class PCAModel(Model):
         return DenseVector(self._ev)
 
     def _transform(self, df):
-        x = df._feature_matrix(self.getInputCol()).to(torch.float64)
-        out = x @ torch.as_tensor(self._pc, device=x.device)
-        return _replace_col(df, self.getOutputCol(), ColumnData(out.contiguous(), None, T.VectorUDT()))
+        x = df._feature_matrix(self.getInputCol())
+        pc = torch.as_tensor(self._pc, device=x.device)
+        if not x.is_cuda:
+            out = (x.to(torch.float64) @ pc).contiguous()
+        else:  # chunk by chunk: no f64 copy of the whole column
+            out = torch.empty((x.shape[0], pc.shape[1]), dtype=torch.float64, device=x.device)
+            for r0 in range(0, x.shape[0], _TRANSFORM_CHUNK):
+                xc = x[r0:r0 + _TRANSFORM_CHUNK]
+                if xc.dtype == torch.float8_e4m3fn:
+                    xc = xc.to(torch.float32)
+                torch.matmul(xc.to(torch.float64), pc, out=out[r0:r0 + _TRANSFORM_CHUNK])
+        return _replace_col(df, self.getOutputCol(), ColumnData(out, None, T.VectorUDT()))
 
     def _save_impl(self, path):
         import pyarrow as pa

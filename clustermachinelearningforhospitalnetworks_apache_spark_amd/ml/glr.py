@@ -5,8 +5,8 @@ Beyond the reference's OLS (ref.py:145-148): length of stay is positive and skew
 model family a user of the reference's LOS regression reaches for next.
 
 Fit = iteratively reweighted least squares, Spark's algorithm (IRLS with absolute
-coefficient change < tol, maxIter 25).  Every IRLS step is ONE pass of the K15 Gram
-kernel over the device-resident rows: ``[X 1 z]ᵀ W [X 1 z]`` accumulated in float64
+coefficient change < tol, maxIter 25).  Every IRLS step is ONE pass of the Gram
+kernel (K15 up to 30 features, K31 for wider bf16 rows) over the device-resident rows: ``[X 1 z]ᵀ W [X 1 z]`` accumulated in float64
 with the working response z and working weights W computed elementwise on the
 device, one all-reduce of (d+2)² doubles, then a (d+1)×(d+1) solve on the host.
 regParam is Spark's L2 penalty on standardized coefficients (WeightedLeastSquares

@@ -3,7 +3,8 @@ DecisionTreeRegressor, RandomForestRegressor.
 
 LinearRegression (Spark defaults maxIter=100, regParam=0, elasticNetParam=0,
 tol=1e-6, fitIntercept=True, standardization=True, solver="auto"): the normal
-equations are built on the device in ONE pass (K15 Gram [X 1 y]ᵀ[X 1 y] in f64),
+equations are built on the device in ONE pass (Gram [X 1 y]ᵀ[X 1 y] in f64: K15 up to
+30 features, K31 on the f64 MFMA for wider bf16 rows, never an n x (d+2) f64 copy),
 all-reduced (C4), and solved on the host in float64 — Cholesky, with ridge in the
 standardized space like Spark's WeightedLeastSquares; L1/elastic-net by coordinate
 descent on the same Gram (same optimum as Spark's OWL-QN); a singular system falls

@@ -5,7 +5,8 @@ The reference only prints model metrics (ref.py:160-198); these are the MLlib
 statistics a user inspects before modelling a feature table such as the
 reference's (ref.py:134-136).  MI355X-first:
 
-* Pearson: the covariance comes from the K15 Gram kernel (``[X 1 0]ᵀ[X 1 0]``
+* Pearson: the covariance comes from the Gram kernels (K15 up to 30 columns, K31 for
+  wider bf16 columns; ``[X 1 0]ᵀ[X 1 0]``
   accumulated in float64 on the device, one all-reduce of (d+2)² doubles), then a
   d×d normalisation on the host.
 * Spearman: global average ranks per column (shards gathered once, ranked by a

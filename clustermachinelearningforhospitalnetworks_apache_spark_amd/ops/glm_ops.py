@@ -407,9 +407,16 @@ def linear_predict(x: torch.Tensor, d: int, coef: torch.Tensor, link: str = "ide
 
 
 def gram(x: torch.Tensor, d: int, y: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[X 1 y]ᵀ W [X 1 y] (float64, (d+2)×(d+2), symmetric) of the local shard."""
+    """[X 1 y]ᵀ W [X 1 y] (float64, (d+2)×(d+2), symmetric) of the local shard. Device rows with d <= 30 run K15;
+    wider bf16 rows (d <= 512) run K31 (``gram_ops.gram``), every other wide device column the chunked f64 form
+    (``gram_ops.gram_reference``): neither makes an n x (d+2) f64 copy."""
     n = x.shape[0]
     m = d + 2
+    if x.is_cuda and d > 30 and n != 0:
+        from . import gram_ops
+        if gram_ops.kernel_supported(x.dtype, d) and gram_ops.kernel_enabled():
+            return gram_ops.gram(x, d, y, weight)
+        return gram_ops.gram_reference(x, d, y, weight)
     if (not x.is_cuda) or d > 30 or n == 0:
         a = torch.cat([x[:, :d].to(torch.float64), torch.ones((n, 1), dtype=torch.float64, device=x.device),
                        y.to(torch.float64).reshape(-1, 1)], 1)

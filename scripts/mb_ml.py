@@ -47,6 +47,13 @@
         reference form (CML_MLP_KERNEL=0), or the dense autograd form on an f64 copy of the same values; for the
         kernel also loss_grad and forward alone with the issued f64 MFMA rate. --pass-only skips the fit
 
+    python scripts/mb_ml.py gram [--rows 4000000] [--dim 256] [--rounds 3] [--fits] [--pass-only]
+        the Gram matrix [X 1 z]^T W [X 1 z] of wide bf16 rows (d > 30, which ``glm`` skips) in three forms,
+        interleaved round by round: the K31 kernel, the chunked reference form, and the dense form on an
+        n x (d + 2) f64 copy (ms, peak allocation rise); --fits adds PCA, LinearRegression(normal) and a 5-step
+        poisson GeneralizedLinearRegression fit on all three; --pass-only times K31 alone with its f64 MFMA rate,
+        for sizes at which the dense form does not fit
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -713,7 +720,94 @@ def cmd_mlp(argv):
         kernel_alone(torch.as_tensor(m.weights.toArray(), device="cuda"))
 
 
-COMMANDS = {"mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_gram(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.feature_extra import PCA
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.regression import (
+        GeneralizedLinearRegression, LinearRegression)
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import gram_ops as GO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    ap = argparse.ArgumentParser(prog="mb_ml.py gram")
+    ap.add_argument("--rows", type=int, default=4_000_000)
+    ap.add_argument("--dim", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--pass-only", action="store_true", help="K31 alone (sizes at which the dense form does not fit)")
+    ap.add_argument("--fits", action="store_true", help="also PCA, LinearRegression and a 5-step poisson GLR fit")
+    a = ap.parse_args(argv)
+    n, d = a.rows, a.dim
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # in chunks: no n x d f32 temporary
+        x[s0:s0 + step] = torch.randn(min(step, n - s0), d, generator=g, device="cuda").to(torch.bfloat16)
+    z = torch.randn(n, generator=g, device="cuda", dtype=torch.float64)
+    w = torch.rand(n, generator=g, device="cuda", dtype=torch.float64)
+    xbytes = x.numel() * x.element_size()
+    nt = (d + 15) // 16
+    flops = 512.0 * ((nt + 1) * (nt + 2) // 2) * n  # 16 x 16 x 4 MFMAs of the upper triangle of (NT + 1)^2 blocks
+
+    def dense(xx, dd, y, weight=None):  # the form before K31: an n x (d + 2) f64 copy (two with weights)
+        aa = torch.cat([xx[:, :dd].to(torch.float64), torch.ones((xx.shape[0], 1), dtype=torch.float64, device=xx.device),
+                        y.to(torch.float64).reshape(-1, 1)], 1)
+        if weight is not None:
+            aa = aa * weight.to(torch.float64).sqrt().reshape(-1, 1)
+        return aa.T @ aa
+
+    def timed(fn, reps=1):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps, torch.cuda.max_memory_allocated() - base, out
+
+    GO.gram(x[:4096], d, z[:4096], w[:4096])  # loads the kernels
+    if a.pass_only:
+        for wt in (None, w):
+            ms = best_ms(lambda: GO.gram(x, d, z, wt), reps=3)
+            print(f"K31 at {n}x{d} bf16{' weighted' if wt is not None else ''}: {ms:.2f} ms, "
+                  f"{flops / ms / 1e9:.2f} TF/s f64 MFMA, {xbytes / ms / 1e9:.3f} TB/s rows", flush=True)
+        return
+    forms = {"kernel": GO.gram, "reference": GO.gram_reference, "dense": dense}
+    for fn in forms.values():
+        fn(x[:100_000], d, z[:100_000], w[:100_000])
+    want = None
+    for r in range(a.rounds):
+        for name, fn in forms.items():
+            s, rise, G = timed(lambda: fn(x, d, z, w))
+            want = G if want is None else want
+            print(f"round {r} gram {n}x{d} weighted [{name}]: {1e3 * s:.2f} ms, peak rise {rise / 2**20:.0f} MiB = "
+                  f"{rise / xbytes:.2f} x the bf16 rows, max rel diff to the first "
+                  f"{float(((G - want).abs() / want.abs().clamp(min=1e-300)).max()):.2e}", flush=True)
+            del G
+    if not a.fits:
+        return
+    spark = SparkSession.builder.master("mi355x").getOrCreate()
+    cnt = torch.poisson(torch.exp(0.3 * x[:, :4].to(torch.float64).sum(1))).to(torch.float64)
+    df = spark.createDataFrameFromTensors({"features": x, "label": z, "count": cnt})
+    small = spark.createDataFrameFromTensors({"features": x[:50_000], "label": z[:50_000], "count": cnt[:50_000]})
+    fits = {"PCA(k=8)": lambda f: PCA(k=8, inputCol="features", outputCol="p").fit(f),
+            "LinearRegression(normal)": lambda f: LinearRegression(solver="normal", regParam=0.1).fit(f),
+            "GLR(poisson, 5 steps)": lambda f: GeneralizedLinearRegression(labelCol="count", family="poisson", maxIter=5,
+                                                                           tol=0.0).fit(f)}
+    real = glm_ops.gram
+    for r in range(a.rounds):
+        for form in ("kernel", "reference", "dense"):
+            os.environ["CML_GRAM_KERNEL"] = "1" if form == "kernel" else "0"
+            glm_ops.gram = dense if form == "dense" else real
+            try:
+                for name, fit in fits.items():
+                    fit(small)
+                    s, rise, _ = timed(lambda: fit(df))
+                    print(f"round {r} {name} {n}x{d} [{form}]: fit {s:.3f} s, peak rise {rise / 2**20:.0f} MiB",
+                          flush=True)
+            finally:
+                glm_ops.gram = real
+    os.environ.pop("CML_GRAM_KERNEL", None)
+
+
+COMMANDS = {"gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
