@@ -6,10 +6,16 @@ fits (ref.py:145-148):
 
     ŷ = b + Σ_i w_i x_i + ½ Σ_f [ (Σ_i v_if x_i)² − Σ_i v_if² x_i² ]
 
-MI355X-first: the interaction term is two [n, d] x [d, f] GEMMs on the device (hipBLASLt) — X·V
-and X²·V² — instead of Spark's per-row loops, and the gradient of the flat parameter vector comes
-from autograd over the same GEMMs; every iteration all-reduces one (1 + d + d·f + 1)-vector of
-gradient sums. Spark's optimiser semantics: ``solver='adamW'`` (β1 0.9, β2 0.999, ε 1e-8, weight
+MI355X-first: a bf16 / e4m3 device column is never converted. bf16 rows inside the limits of K32
+(``ops/fm_ops.py``, ``_native/csrc/fm.hip``: padded width 16..512, factorSize <= 31, <= 15 at width
+512) take one fused f64-MFMA pass per iteration that reads every selected row once: the narrow
+product X·[V | w], the per-row loss and residual, and the transposed product back, with the
+second-order term as one dot product against Σ_f v_if² forward and one vector Σ_rows r x_i² backward.
+A mini-batch is a row list, not a copy. Other low-precision columns (and ``CML_FM_KERNEL=0``) take
+the chunked f64 reference form of the same arithmetic; transform routes the same way. f32 / f64
+columns and CPU frames keep the dense form: two [n, d] x [d, f] GEMMs (hipBLASLt) — X·V and X²·V² —
+with the gradient of the flat parameter vector from autograd over them. Every iteration all-reduces
+one (1 + d + d·f + 2)-vector of gradient sums, loss and count. Spark's optimiser semantics: ``solver='adamW'`` (β1 0.9, β2 0.999, ε 1e-8, weight
 decay regParam) or ``'gd'`` (step stepSize / sqrt(iteration)), mini-batches of ``miniBatchFraction``
 drawn per iteration by hash(seed + iteration, row id) (GPU-count invariant), stop when the parameter
 change is below tol · max(‖w‖, 1).
@@ -58,6 +64,18 @@ def _fm_scores(x: torch.Tensor, b, w, V) -> torch.Tensor:
     return b + x @ w + 0.5 * (xv * xv - x2v2).sum(1)
 
 
+def _low_precision(x: torch.Tensor) -> bool:
+    """bf16 and e4m3 device columns: the path without an f64 copy. Every other column keeps the dense form."""
+    return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
+
+
+def _use_kernel(x: torch.Tensor, f: int) -> bool:
+    from ..ops import fm_ops as FO
+    from ..utils.device import padded_dim
+    return (x.dtype == torch.bfloat16 and FO.kernel_enabled()
+            and FO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), f))
+
+
 class _FMBase(Estimator):
     _loss = "squared"
 
@@ -69,7 +87,10 @@ class _FMBase(Estimator):
     def _fit(self, df):
         from ..utils import rng
         from .tree_models import _default_seed
-        x = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
+        x = df._feature_matrix(self.getFeaturesCol())
+        lowp = _low_precision(x)
+        if not lowp:
+            x = x.to(torch.float64)
         n, d = x.shape
         y = df._column_data(self.getLabelCol()).values.to(torch.float64)
         comm = df._comm
@@ -91,22 +112,38 @@ class _FMBase(Estimator):
         m2 = np.zeros_like(p)
         hist = []
         rows = df._row_ids
+        if lowp:
+            # the rows as they are: K32 on bf16 rows inside its limits, the chunked reference form otherwise
+            from ..ops import fm_ops as FO
+            kernel = _use_kernel(x, f)
+            if kernel:
+                from ..models.kmeans import to_device_matrix
+                x = to_device_matrix(x, d)  # a copy only when the layout is not already the kernel's
+            y = y.contiguous()
         it = 0
         for it in range(1, self.getMaxIter() + 1):
-            if frac < 1.0:
-                sel = rng.uniform(rows, seed + it, stream=11) < frac
-                xb, yb = x[sel], y[sel]
+            if lowp:
+                # a mini-batch is a row list: no rows are copied
+                sel = torch.nonzero(rng.uniform(rows, seed + it, stream=11) < frac).reshape(-1) if frac < 1.0 else None
+                pt = torch.as_tensor(p, device=x.device)
+                gl = (FO.loss_grad if kernel else FO.loss_grad_reference)(x, sel, d, y, pt, f, self._loss)
+                cnt = n if sel is None else sel.numel()
+                msg = torch.cat([gl, torch.tensor([float(cnt)], dtype=torch.float64, device=x.device)])
             else:
-                xb, yb = x, y
-            pt = torch.as_tensor(p, device=x.device).requires_grad_(True)
-            s = _fm_scores(xb, pt[0], pt[1:1 + d], pt[1 + d:].reshape(d, f))
-            if self._loss == "logistic":
-                loss = (torch.nn.functional.softplus(s) - yb * s).sum()
-            else:
-                loss = 0.5 * ((s - yb) ** 2).sum()
-            grad, = torch.autograd.grad(loss, pt)
-            msg = torch.cat([grad.detach(), loss.detach().reshape(1),
-                             torch.tensor([float(yb.numel())], dtype=torch.float64, device=x.device)])
+                if frac < 1.0:
+                    sel = rng.uniform(rows, seed + it, stream=11) < frac
+                    xb, yb = x[sel], y[sel]
+                else:
+                    xb, yb = x, y
+                pt = torch.as_tensor(p, device=x.device).requires_grad_(True)
+                s = _fm_scores(xb, pt[0], pt[1:1 + d], pt[1 + d:].reshape(d, f))
+                if self._loss == "logistic":
+                    loss = (torch.nn.functional.softplus(s) - yb * s).sum()
+                else:
+                    loss = 0.5 * ((s - yb) ** 2).sum()
+                grad, = torch.autograd.grad(loss, pt)
+                msg = torch.cat([grad.detach(), loss.detach().reshape(1),
+                                 torch.tensor([float(yb.numel())], dtype=torch.float64, device=x.device)])
             comm.allreduce_(msg)
             o = msg.cpu().numpy()
             cnt = max(o[-1], 1.0)
@@ -164,6 +201,16 @@ class _FMModelBase(Model):
 
     def _scores(self, x: torch.Tensor) -> torch.Tensor:
         dev = x.device
+        if _low_precision(x):  # no f64 copy of the rows: ops/fm_ops.py
+            from ..ops import fm_ops as FO
+            d, f = int(x.shape[1]), int(self._V.shape[1])
+            if d != self._w.size:
+                raise ValueError(f"{type(self).__name__}: {self._w.size} features fitted, the column has {d}")
+            p = torch.as_tensor(np.concatenate([[self._b], self._w, self._V.reshape(-1)]), device=dev)
+            if _use_kernel(x, f):
+                from ..models.kmeans import to_device_matrix
+                return FO.scores(to_device_matrix(x, d), d, p, f)
+            return FO.scores_reference(x, d, p, f)
         return _fm_scores(x.to(torch.float64), self._b, torch.as_tensor(self._w, device=dev),
                           torch.as_tensor(self._V, device=dev))
 
@@ -204,18 +251,22 @@ class FMClassificationModel(_FMModelBase):
     def _transform(self, df):
         s = self._scores(df._feature_matrix(self.getFeaturesCol()))
         p1 = torch.sigmoid(s)
-        prob = torch.stack([1 - p1, p1], 1)
         out = df
         if self.getRawPredictionCol():
             out = _replace_col(out, self.getRawPredictionCol(), ColumnData(torch.stack([-s, s], 1), None,
                                                                           T.VectorUDT()))
+        del s  # the columns below are built in place: no temporary of the scores' size outlives its statement
+        prob = torch.empty((p1.shape[0], 2), dtype=p1.dtype, device=p1.device)
+        torch.neg(p1, out=prob[:, 0])
+        prob[:, 0] += 1  # -p1 + 1 rounds as 1 - p1 does
+        prob[:, 1] = p1
         if self.getProbabilityCol():
             out = _replace_col(out, self.getProbabilityCol(), ColumnData(prob, None, T.VectorUDT()))
         thr = self.getOrDefault("thresholds") if self.isSet("thresholds") else None
         if thr:
             pred = torch.argmax(prob / torch.as_tensor(np.asarray(thr, dtype=np.float64), device=prob.device), 1)
         else:
-            pred = (p1 > 0.5).to(torch.int64)
+            pred = p1 > 0.5
         return _replace_col(out, self.getPredictionCol(), ColumnData(pred.to(torch.float64), None, T.DoubleType()))
 
     def predict(self, value) -> float:

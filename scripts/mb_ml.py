@@ -54,6 +54,14 @@
         poisson GeneralizedLinearRegression fit on all three; --pass-only times K31 alone with its f64 MFMA rate,
         for sizes at which the dense form does not fit
 
+    python scripts/mb_ml.py fm [--rows 20000000] [--dim 64] [--factor-size 8] [--max-iter 10] [--rounds 2]
+                               [--loss squared|logistic] [--pass-only]
+        one loss + gradient evaluation of the factorisation machine and an FMRegressor / FMClassifier fit on bf16
+        rows in three forms, interleaved round by round in one process: the K32 kernel, the chunked reference form
+        (CML_FM_KERNEL=0), and the dense autograd form on an f64 copy of the same values (ms or s, peak allocation
+        rise); then K32's loss_grad and scores alone with the issued f64 MFMA rate. --pass-only times K32 alone,
+        for sizes at which the dense form does not fit
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -720,6 +728,105 @@ def cmd_mlp(argv):
         kernel_alone(torch.as_tensor(m.weights.toArray(), device="cuda"))
 
 
+def cmd_fm(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml import fm as FM
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.regression import FMRegressor
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import fm_ops as FO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    ap = argparse.ArgumentParser(prog="mb_ml.py fm")
+    ap.add_argument("--rows", type=int, default=20_000_000)
+    ap.add_argument("--dim", type=int, default=64)
+    ap.add_argument("--factor-size", type=int, default=8)
+    ap.add_argument("--max-iter", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--loss", choices=["squared", "logistic"], default="squared")
+    ap.add_argument("--pass-only", action="store_true", help="K32 alone (sizes at which the dense form does not fit)")
+    a = ap.parse_args(argv)
+    n, d, f = a.rows, a.dim, a.factor_size
+    g = torch.Generator(device="cuda").manual_seed(1)
+    w = torch.randn(d, generator=g, device="cuda") / d ** 0.5
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    y = torch.empty(n, dtype=torch.float64, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # a planted linear rule with noise, in chunks: no n x d f32 temporary
+        v = torch.randn(min(step, n - s0), d, generator=g, device="cuda")
+        x[s0:s0 + step] = v.to(torch.bfloat16)
+        y[s0:s0 + step] = v @ w + 0.5 * torch.randn(len(v), generator=g, device="cuda")
+        del v
+    if a.loss == "logistic":
+        y = (y > 0).to(torch.float64)
+    xd = to_device_matrix(x, d)
+    del x
+    dp = int(xd.shape[1])
+    xbytes = xd.numel() * xd.element_size()
+    import numpy as np
+    rs = np.random.RandomState(3)
+    p = torch.as_tensor(np.concatenate([[0.3], rs.randn(d) / np.sqrt(d), 0.5 * rs.randn(d * f) / np.sqrt(d)]),
+                        device="cuda")
+    hp = 16 if f <= 15 else 32
+    # MFMAs issued per 64-row tile: the forward and the blocks of dP, hp / 16 * dp / 16 * 16 each
+    flops = ((n + 63) // 64) * 2 * 16 * (hp // 16) * (dp // 16) * 2048.0
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, torch.cuda.max_memory_allocated() - base, out
+
+    FO.loss_grad(xd[:4096], None, d, y[:4096], p, f, a.loss)  # loads the kernels
+    if a.pass_only:
+        ms = best_ms(lambda: FO.loss_grad(xd, None, d, y, p, f, a.loss), reps=3)
+        print(f"K32 loss_grad at {n}x{d} bf16 factorSize={f} {a.loss}: {ms:.2f} ms, {flops / ms / 1e9:.2f} TF/s f64 MFMA "
+              f"issued, {xbytes / ms / 1e9:.3f} TB/s rows", flush=True)
+        ms = best_ms(lambda: FO.scores(xd, d, p, f), reps=3)
+        print(f"K32 scores: {ms:.2f} ms, {xbytes / ms / 1e9:.3f} TB/s rows", flush=True)
+        return
+    x64 = xd[:, :d].to(torch.float64)  # the dense form's column (its conversion is not timed)
+
+    def dense():
+        pt = p.clone().requires_grad_(True)
+        s = FM._fm_scores(x64, pt[0], pt[1:1 + d], pt[1 + d:].reshape(d, f))
+        loss = (torch.nn.functional.softplus(s) - y * s).sum() if a.loss == "logistic" else 0.5 * ((s - y) ** 2).sum()
+        grad, = torch.autograd.grad(loss, pt)
+        return torch.cat([grad, loss.detach().reshape(1)])
+
+    forms = {"kernel": lambda: FO.loss_grad(xd, None, d, y, p, f, a.loss),
+             "reference": lambda: FO.loss_grad_reference(xd, None, d, y, p, f, a.loss), "dense": dense}
+    spark = SparkSession.builder.master("mi355x").getOrCreate()
+    frames = {"kernel": spark.createDataFrameFromTensors({"features": xd[:, :d], "label": y}),
+              "dense": spark.createDataFrameFromTensors({"features": x64, "label": y})}
+    frames["reference"] = frames["kernel"]
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.classification import FMClassifier
+    est = (FMClassifier if a.loss == "logistic" else FMRegressor)(factorSize=f, seed=3, maxIter=a.max_iter, tol=0.0,
+                                                                   stepSize=0.05)
+    want = None
+    for r in range(a.rounds):
+        for name, fn in forms.items():
+            fn()
+            s, rise, out = timed(fn)
+            want = out if want is None else want
+            print(f"round {r} fm {n}x{d} factorSize={f} {a.loss} one iteration [{name}]: {1e3 * s:.2f} ms, peak rise "
+                  f"{rise / 2**20:.0f} MiB = {rise / xbytes:.2f} x the bf16 rows, max rel diff to the first "
+                  f"{float(((out - want).abs() / want.abs().clamp(min=1e-300)).max()):.2e}", flush=True)
+            del out
+        for name in forms:
+            os.environ["CML_FM_KERNEL"] = "1" if name == "kernel" else "0"
+            s, rise, m = timed(lambda: est.fit(frames[name]))
+            print(f"round {r} fm {n}x{d} factorSize={f} {a.loss} fit maxIter={a.max_iter} [{name}]: {s:.3f} s, final "
+                  f"loss {m._hist[-1]:.12e}, peak rise {rise / 2**20:.0f} MiB = {rise / xbytes:.2f} x the bf16 rows",
+                  flush=True)
+    os.environ.pop("CML_FM_KERNEL", None)
+    ms = best_ms(forms["kernel"], reps=3)
+    print(f"K32 loss_grad alone: {ms:.2f} ms, {flops / ms / 1e9:.2f} TF/s f64 MFMA issued, {xbytes / ms / 1e9:.3f} TB/s "
+          f"rows", flush=True)
+    ms = best_ms(lambda: FO.scores(xd, d, p, f), reps=3)
+    print(f"K32 scores alone: {ms:.2f} ms, {xbytes / ms / 1e9:.3f} TB/s rows", flush=True)
+
+
 def cmd_gram(argv):
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.feature_extra import PCA
     from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.regression import (
@@ -807,7 +914,7 @@ def cmd_gram(argv):
     os.environ.pop("CML_GRAM_KERNEL", None)
 
 
-COMMANDS = {"gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+COMMANDS = {"fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
