@@ -29,7 +29,7 @@
 // d_L - d_R by at most 2 (dp + 2) u (|x|^2 + (|c_L|^2 + |c_R|^2) / 2) for euclidean and the computed
 // x·delta / |x| by at most (dp + 2) u · 2 for cosine; tests/test_bisect_step_gpu.py allows choices to differ
 // from an f64 oracle inside four times these bands only.
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
         d0 = delta[(long long)dslot * dp + 2 * p];
         d1 = delta[(long long)dslot * dp + 2 * p + 1];
       }
-      s[k] = (double)__uint_as_float(xv[k] << 16) * d0 + (double)__uint_as_float(xv[k] & 0xffff0000u) * d1;
+      s[k] = bf16hi_to_f64(xv[k] << 16) * d0 + bf16hi_to_f64(xv[k] & 0xffff0000u) * d1;
     }
     // over the unit's threads: a butterfly inside the wave (every lane ends with the same bits) ...
     for (int o = 1; o < lanes; o <<= 1) {
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
       if (p == 0) choice[ib + k] = go ? 1 : 0;
       if (want_sums && (al_cur || ar_cur)) {
         const double wl = go ? 0.0 : om[k], wr = go ? om[k] : 0.0;
-        const double x0 = (double)__uint_as_float(xv[k] << 16), x1 = (double)__uint_as_float(xv[k] & 0xffff0000u);
+        const double x0 = bf16hi_to_f64(xv[k] << 16), x1 = bf16hi_to_f64(xv[k] & 0xffff0000u);
         aL0 += wl * x0;
         aL1 += wl * x1;
         aR0 += wr * x0;

@@ -41,3 +41,29 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 
 // Host-side launch status helper.
 static inline int cml_status() { return (int)hipGetLastError(); }
+
+constexpr long long kLdsPerCu = 160 * 1024;  // LDS bytes of a CU
+
+// Workgroups of a persistent launch over `tiles` tiles: per_cu for every CU (256 CUs where the count is unknown).
+static inline long long cml_grid_cap(long long tiles, int ncu, long long per_cu) {
+  const long long cap = (long long)(ncu > 0 ? ncu : 256) * per_cu;
+  return tiles < cap ? tiles : cap;
+}
+
+// Launch with `lds` bytes of dynamic LDS: raises the kernel's limit first; a failure of that call is the launch's
+// error.
+template <typename... KArgs, typename... Args>
+static inline int cml_launch_lds(void (*kernel)(KArgs...), int grid, int block, long long lds, hipStream_t st,
+                                 Args... args) {
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)block), (size_t)lds, st, (KArgs)args...);
+  return cml_status();
+}
+
+// Launch of a fold kernel: one thread of a 256-thread workgroup per output element.
+template <typename... KArgs, typename... Args>
+static inline int cml_launch_fold(void (*kernel)(KArgs...), long long ne, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, (KArgs)args...);
+  return cml_status();
+}

@@ -16,8 +16,8 @@
 //             order). The global loads of a tile are issued one tile ahead and wait in registers while the
 //             previous tile is computed.
 //   forward   a wave owns 16 rows, row = lane & 15, lane group g = lane >> 4, transposed on
-//             v_mfma_f64_16x16x4_f64 (lane l: A[row l&15][k l>>4], B[k l>>4][col l&15]; results col = l&15,
-//             row = (l>>4) + 4 reg): T^T[unit][row] = P[unit][k] X^T[k][row]. The x^2 sv term is one multiply and
+//             v_mfma_f64_16x16x4_f64 (operand layout: mfma64.h): T^T[unit][row] = P[unit][k] X^T[k][row]. The x^2
+//             sv term is one multiply and
 //             one FMA per K-step on the operand the lane already holds; it, sum_u t_u^2 and the linear unit are
 //             summed over the four lane groups. s, l and r are f64 VALU; rows past the end get r = 0 and no loss.
 //             Column blocks go in pairs on two accumulation chains, and the LDS operands of a pair (x, P, sv) are
@@ -35,14 +35,13 @@
 //
 // LDS reads of a half wave fall on 32 distinct doubles mod 32: the image uses K29's XOR of the column index with
 // f(unit) = 2 (unit & 15) ^ 16 (unit & 1); the staging buffer has pitch 66 (2 c + g).
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
 constexpr int kFmThreads = 256;
 constexpr int kFmTile = 64;   // rows per tile: 16 per wave
 constexpr int kFmSP = 66;     // f64 pitch of a staging row (64 rows of a tile)
-typedef double fm_f64x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int fm_dpt(int dp) { return dp < 64 ? 64 : dp; }  // compiled width class
 
@@ -55,14 +54,10 @@ __host__ __device__ constexpr long long fm_lds_bytes(int dpt, int t) {
 
 __host__ __device__ constexpr bool fm_supported(int dp, int t) {
   if (dp < 16 || dp > 512 || (dp & (dp - 1)) != 0 || t < 1 || t > 2) return false;
-  return fm_lds_bytes(fm_dpt(dp), t) <= 160 * 1024;
+  return fm_lds_bytes(fm_dpt(dp), t) <= kLdsPerCu;
 }
 
 __host__ __device__ constexpr long long fm_part_len(int dp, int t) { return (long long)16 * t * dp + dp + 2; }
-
-__device__ __forceinline__ double fm_bf16(unsigned bits16_in_high_half) {
-  return (double)__uint_as_float(bits16_in_high_half);
-}
 
 template <int DPT, int T>
 __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int nb = dp >> 4;               // 16-column blocks of a row
 
-  auto psw = [](int unit, int col) { return unit * BP + (col ^ ((2 * (unit & 15)) ^ (16 * (unit & 1)))); };
+  auto psw = [](int unit, int col) { return unit * BP + unit_swizzle(unit, col); };
 
   for (int i = tid; i < HP * dp; i += kFmThreads) Ps[psw(i / dp, i % dp)] = wp[i];
   const double bias = wp[(long long)HP * dp];
@@ -101,19 +96,20 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
 
   int unit_of[NI];
 #pragma unroll
-  for (int i = 0; i < NI; ++i) unit_of[i] = 16 * (i >> 2) + g + 4 * (i & 3);
+  for (int i = 0; i < NI; ++i) unit_of[i] = unit_of_lane(i, g);
 
-  fm_f64x4 gp[NBW];
+  f64x4 gp[NBW];
   double uacc[NBW];
 #pragma unroll
   for (int s = 0; s < NBW; ++s) {
-    gp[s] = (fm_f64x4)0.0;
+    gp[s] = (f64x4)0.0;
     uacc[s] = 0.0;
   }
   double dbacc = 0.0, lossacc = 0.0;
 
   const long long ntiles = (B + kFmTile - 1) / kFmTile;
-  const long long t0 = ntiles * blockIdx.x / gridDim.x, t1 = ntiles * (blockIdx.x + 1) / gridDim.x;
+  long long t0, t1;
+  tile_run(ntiles, t0, t1);
 
   // The row of the matrix behind row ri of the walk; -1 = none (past the end, or a listed index outside [0, n)).
   auto source = [&](long long ri) -> long long {
@@ -152,6 +148,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
       const int item = tid + kFmThreads * j;
       if (item < kFmTile * nb) {
         const int row = item >> lnb, tb = item & (nb - 1);
+        // the same block as in lda.hip and mlp.hip: as a shared function it compiles to other machine code
         const unsigned w[8] = {pf[j][0].x, pf[j][0].y, pf[j][0].z, pf[j][0].w,
                                pf[j][1].x, pf[j][1].y, pf[j][1].z, pf[j][1].w};
         unsigned v[16];
@@ -176,12 +173,12 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
     if (tile + 1 < t1) fetch(tile + 1);
     double cur[NI], q;
     {
-      fm_f64x4 z[2][T];  // two chains of column blocks
+      f64x4 z[2][T];  // two chains of column blocks
       double qq[2] = {0.0, 0.0};
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        z[0][t] = (fm_f64x4)0.0;
-        z[1][t] = (fm_f64x4)0.0;
+        z[0][t] = (f64x4)0.0;
+        z[1][t] = (f64x4)0.0;
       }
       const u16* xrow = Xs + (wave * 16 + c) * XP + 4 * g;
       // The LDS operands of a pair of column blocks (chain 0: the even block, chain 1: the odd one). A pair's
@@ -208,10 +205,10 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
         double xs[2][4];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          xs[u][0] = fm_bf16(o.xv[u].x << 16);
-          xs[u][1] = fm_bf16(o.xv[u].x & 0xffff0000u);
-          xs[u][2] = fm_bf16(o.xv[u].y << 16);
-          xs[u][3] = fm_bf16(o.xv[u].y & 0xffff0000u);
+          xs[u][0] = bf16hi_to_f64(o.xv[u].x << 16);
+          xs[u][1] = bf16hi_to_f64(o.xv[u].x & 0xffff0000u);
+          xs[u][2] = bf16hi_to_f64(o.xv[u].y << 16);
+          xs[u][3] = bf16hi_to_f64(o.xv[u].y & 0xffff0000u);
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -253,9 +250,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
         lin += unit_of[i] == f ? cur[i] : 0.0;
       }
       double h = lin + 0.5 * (sq - q);
-      h += __shfl_xor(h, 16, 64);
-      h += __shfl_xor(h, 32, 64);
-      s = bias + h;
+      s = bias + lane_groups_sum(h);
     }
 
     if (!fit) {
@@ -313,7 +308,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
         if ((4 * slot + wave) / T < nb) {
 #pragma unroll
           for (int s4 = 0; s4 < 16; ++s4) {
-            const double xv = fm_bf16(xq[slot & 1][s4] << 16);
+            const double xv = bf16hi_to_f64(xq[slot & 1][s4] << 16);
             gp[slot] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[s4], xv, gp[slot], 0, 0, 0);
             if (tw == 0) uacc[slot] = fma(dr[s4], xv * xv, uacc[slot]);
           }
@@ -334,9 +329,7 @@ __global__ __launch_bounds__(kFmThreads, 1) void fm_pass_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) pp[(long long)(16 * t + g + 4 * r) * dp + 16 * tb + c] = gp[slot][r];
         if (t == 0) {
-          double v = uacc[slot];
-          v += __shfl_xor(v, 16, 64);
-          v += __shfl_xor(v, 32, 64);
+          const double v = lane_groups_sum(uacc[slot]);
           if (g == 0) pu[16 * tb + c] = v;
         }
       }
@@ -395,14 +388,8 @@ int fm_launch(int grid, hipStream_t st, const void* X, long long n, int dp, int 
   if constexpr (!fm_supported(DPT, T)) {
     return (int)hipErrorInvalidValue;
   } else {
-    const long long lds = fm_lds_bytes(DPT, T);
-    // raise the dynamic LDS limit first; a failure of that call is this launch's error
-    const hipError_t e = hipFuncSetAttribute((const void*)fm_pass_kernel<DPT, T>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((fm_pass_kernel<DPT, T>), dim3((unsigned)grid), dim3(kFmThreads), (size_t)lds, st,
-                       (const u16*)X, n, dp, d, f, rows, B, y, wp, part, out, fit, logistic);
-    return cml_status();
+    return cml_launch_lds(fm_pass_kernel<DPT, T>, grid, kFmThreads, fm_lds_bytes(DPT, T), st, (const u16*)X, n, dp, d, f,
+                          rows, B, y, wp, part, out, fit, logistic);
   }
 }
 
@@ -428,9 +415,7 @@ CML_API long long cml_fm_lds(int dp, int f) {
 // or no row.
 CML_API int cml_fm_grid(long long B, int dp, int f, int ncu) {
   if (cml_fm_lds(dp, f) == 0 || B <= 0) return 0;
-  const long long tiles = (B + kFmTile - 1) / kFmTile;
-  const long long cap = ncu > 0 ? ncu : 256;
-  return (int)(tiles < cap ? tiles : cap);
+  return (int)cml_grid_cap((B + kFmTile - 1) / kFmTile, ncu, 1);
 }
 
 // X: bf16 [n, dp] contiguous; rows: i64 [B] (indices into X; one outside [0, n) counts as no row) or null for the
@@ -455,7 +440,5 @@ CML_API int cml_fm_pass(const void* X, long long n, int dp, int d, int f, const 
   }
   if (rc != 0 || !fit) return rc;
   const long long ne = 2 + d + (long long)d * f;
-  hipLaunchKernelGGL(fm_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, part, grid, 16 * t, dp, d, f, wp,
-                     out);
-  return cml_status();
+  return cml_launch_fold(fm_fold_kernel, ne, st, part, grid, 16 * t, dp, d, f, wp, out);
 }

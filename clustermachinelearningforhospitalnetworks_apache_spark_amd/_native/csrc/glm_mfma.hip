@@ -20,7 +20,7 @@
 // accumulators per lane); C > 32 with dpad > 128 runs as two launches (FTG = FT / 2: more accumulators spilled),
 // each recomputing the margins from every feature (X re-read from HBM).
 // Rows: bf16 with d % 8 == 0 (16-byte chunks), any row stride ld % 8 == 0.
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
@@ -800,15 +800,14 @@ CML_API int cml_multinomial_mfma_grad(const void* X, long long n, long long ld, 
 // ---------------------------------------------------------------------------------------------------------------
 // K13t: multinomial LogisticRegressionModel.transform — raw margins X·Wᵀ + b and the softmax probabilities, in
 // f64 as Spark computes them (LogisticRegressionModel.predictRaw / raw2probabilityInPlace), one pass over X.
-// The products run on v_mfma_f64_16x16x4_f64 (f64 accumulation; the bf16 / f32 rows convert exactly), 16 rows
-// per wave tile: lane l holds A = X[row l&15][k = l>>4] and B = W[k = l>>4][class l&15]; the k index of step s
+// The products run on v_mfma_f64_16x16x4_f64 (f64 accumulation; the bf16 / f32 rows convert exactly; operand
+// layout: mfma64.h), 16 rows per wave tile with A = X and B = W[k][class]; the k index of step s
 // of lane quarter kq is feature kq·K4 + s, so every lane walks a contiguous run of its row (K4 = DP/4 values,
 // loaded once into registers). Results: col = class (lane&15), row = (lane>>4) + 4·reg. The softmax over a
 // row's classes is a 16-lane reduction per register. W (f64, padded to 16-class blocks) lives in LDS.
 namespace {
 
 constexpr int kPtThreads = 256;
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 template <typename T, int K4, int CB>
 __global__ __launch_bounds__(kPtThreads) void multinomial_predict_kernel(const T* __restrict__ X, long long n,
@@ -922,7 +921,7 @@ CML_API long long cml_multinomial_predict_lds(int d, int dtype, int C) {
   if ((dtype != 0 && dtype != 1) || d < 1 || d > 256 || C < 1 || C > 64) return 0;
   const int k4 = ((d + 31) / 32) * 8, cp = 16 * ((C + 15) / 16);
   const long long lds = (long long)cp * (4 * k4 + 1) * 8 + cp * 8;
-  return lds <= 160 * 1024 ? lds : 0;
+  return lds <= kLdsPerCu ? lds : 0;
 }
 
 // raw, prob: f64 [n, C] row-major; coef [C][d+1] f64 (last column the intercepts).
@@ -936,10 +935,8 @@ CML_API int cml_multinomial_predict(const void* X, long long n, long long ld, in
   if ((reinterpret_cast<size_t>(X) & 15) != 0 || (ld * esz) % 16 != 0 || ld < d) return (int)hipErrorInvalidValue;
   const int k4 = ((d + 31) / 32) * 8, cb = (C + 15) / 16;
   const long long tiles = (n + 15) / 16;
-  const int per_cu = (int)((160 * 1024) / lds) > 0 ? (int)((160 * 1024) / lds) : 1;
-  long long grid = (tiles + 3) / 4;
-  const long long cap = (long long)(ncu > 0 ? ncu : 256) * (per_cu < 4 ? per_cu : 4);
-  grid = grid < cap ? grid : cap;
+  const int per_cu = (int)(kLdsPerCu / lds) > 0 ? (int)(kLdsPerCu / lds) : 1;
+  const long long grid = cml_grid_cap((tiles + 3) / 4, ncu, per_cu < 4 ? per_cu : 4);
   hipStream_t st = (hipStream_t)stream;
 #define CML_MNP(TT, K4V, CBV)                                                                                  \
   if (k4 == K4V && cb == CBV) {                                                                                \

@@ -4,9 +4,7 @@
 // is lp_j = c_j - |A_j (x - mu_j)|^2 / 2; its responsibility is r_j = w exp(lp_j - lse) with lse the
 // log-sum-exp over the components, and the M-step needs, per component, S0 = sum r, S1 = sum r x and
 // S2 = sum r x x^T. Both the Mahalanobis terms and the second moments are small GEMMs and run on
-// v_mfma_f64_16x16x4_f64 (lane l: A[row l&15][k l>>4], B[k l>>4][col l&15]; results col = l&15,
-// row = (l>>4) + 4 reg: the f64 form, not the bf16 C/D map). Every value after the exact bf16 -> f64 widening
-// is f64.
+// v_mfma_f64_16x16x4_f64 (operand layout: mfma64.h). Every value after the exact bf16 -> f64 widening is f64.
 //
 // A workgroup of 512 threads (8 waves) keeps the tables [A_j^T | mu | c] in LDS for the whole launch and walks a
 // contiguous run of row tiles (TR = 2048 / DP rows: 128 at DP = 16, 64 at DP = 32). Per tile:
@@ -22,13 +20,12 @@
 // At the end every workgroup writes its partial [k][1 + d + d*d] (the lower triangle of S2 mirrored, so S2 is
 // symmetric bit for bit) and its two tail sums; gmm_fold_kernel adds the partials in workgroup order. No
 // atomics, nothing of size n x k or n x d in global memory, and the grid depends on (n, DP, k, CUs) only.
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
 constexpr int kGmThreads = 512;
 constexpr int kGmWaves = 8;
-typedef double gm_f64x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int gm_rp(int k) { return k | 1; }  // odd f64 pitch of R: rows on distinct banks
 
@@ -65,7 +62,8 @@ __global__ __launch_bounds__(kGmThreads) void gmm_estep_kernel(const u16* __rest
   for (int i = tid; i < ntab; i += kGmThreads) Bt[i] = tab[i];
 
   const long long ntiles = (n + TR - 1) / TR;
-  const long long t0 = ntiles * blockIdx.x / gridDim.x, t1 = ntiles * (blockIdx.x + 1) / gridDim.x;
+  long long t0, t1;
+  tile_run(ntiles, t0, t1);
   const int lrow = (4 * tid) / DP, lcol = (4 * tid) % DP;
 
   uint2 xq = make_uint2(0u, 0u);
@@ -79,12 +77,12 @@ __global__ __launch_bounds__(kGmThreads) void gmm_estep_kernel(const u16* __rest
     }
   };
 
-  gm_f64x4 S2[MAXC][NT];
+  f64x4 S2[MAXC][NT];
   double s1[MAXC][CB], s0[MAXC];
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) S2[c][t] = (gm_f64x4)0.0;
+    for (int t = 0; t < NT; ++t) S2[c][t] = (f64x4)0.0;
 #pragma unroll
     for (int b = 0; b < CB; ++b) s1[c][b] = 0.0;
     s0[c] = 0.0;
@@ -98,8 +96,8 @@ __global__ __launch_bounds__(kGmThreads) void gmm_estep_kernel(const u16* __rest
       const unsigned wv[2] = {xq.x, xq.y};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float v = __uint_as_float((e & 1) ? (wv[e >> 1] & 0xffff0000u) : (wv[e >> 1] << 16));
-        Xs[lrow * XP + lcol + e] = lcol + e < d ? (double)v : 0.0;
+        const double v = bf16hi_to_f64((e & 1) ? (wv[e >> 1] & 0xffff0000u) : (wv[e >> 1] << 16));
+        Xs[lrow * XP + lcol + e] = lcol + e < d ? v : 0.0;
       }
       if (tid < TR) wl[tid] = wq;
     }
@@ -112,9 +110,9 @@ __global__ __launch_bounds__(kGmThreads) void gmm_estep_kernel(const u16* __rest
       const double* xs = Xs + (g * 16 + r16) * XP;
       const double* mj = mu + j * DP;
       const double* bt = Bt + (long long)j * DP * DP + r16;
-      gm_f64x4 D[CB];
+      f64x4 D[CB];
 #pragma unroll
-      for (int cb = 0; cb < CB; ++cb) D[cb] = (gm_f64x4)0.0;
+      for (int cb = 0; cb < CB; ++cb) D[cb] = (f64x4)0.0;
 #pragma unroll
       for (int s = 0; s < DP / 4; ++s) {
         const int t = 4 * s + kq;
@@ -221,15 +219,11 @@ __global__ __launch_bounds__(kGmThreads) void gmm_estep_kernel(const u16* __rest
       const int j = wave + kGmWaves * c;
       if (j < k) {
         double* out = pp + cs * j;
-        double v = s0[c];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
+        const double v = lane_groups_sum(s0[c]);
         if (lane == 0) out[0] = v;
 #pragma unroll
         for (int b = 0; b < CB; ++b) {
-          double u = s1[c][b];
-          u += __shfl_xor(u, 16, 64);
-          u += __shfl_xor(u, 32, 64);
+          const double u = lane_groups_sum(s1[c][b]);
           if (kq == 0 && 16 * b + r16 < d) out[1 + 16 * b + r16] = u;
         }
         double* o2 = out + 1 + d;
@@ -276,16 +270,11 @@ bool gm_args_ok(const void* X, long long n, int dp, int d, int k) {
   return (reinterpret_cast<size_t>(X) & 7) == 0;  // the 8-byte row loads
 }
 
-// One launch of either form: raises the kernel's dynamic LDS limit first and returns that call's error if it fails.
 template <int DP, bool PREDICT>
 int gm_launch(int grid, long long lds, hipStream_t st, const void* X, long long n, int d, int k, const double* wts,
               const double* tab, double* part, double* prob, int* label) {
-  const hipError_t e = hipFuncSetAttribute((const void*)gmm_estep_kernel<DP, PREDICT>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((gmm_estep_kernel<DP, PREDICT>), dim3((unsigned)grid), dim3(kGmThreads), (size_t)lds, st,
-                     (const u16*)X, n, d, k, wts, tab, part, prob, label);
-  return cml_status();
+  return cml_launch_lds(gmm_estep_kernel<DP, PREDICT>, grid, kGmThreads, lds, st, (const u16*)X, n, d, k, wts, tab, part,
+                        prob, label);
 }
 
 template <bool PREDICT>
@@ -301,7 +290,7 @@ int gm_launch_dp(int dp, int grid, long long lds, hipStream_t st, const void* X,
 CML_API long long cml_gmm_lds(int dp, int k) {
   if ((dp != 16 && dp != 32) || k < 2 || k > (dp == 16 ? 32 : 16)) return 0;
   const long long lds = gm_lds_doubles(dp, k) * 8;
-  return lds <= 160 * 1024 ? lds : 0;
+  return lds <= kLdsPerCu ? lds : 0;
 }
 
 // Workgroups of a launch: a function of (n, dp, k, CUs) only. 0 = unsupported or no rows. The fit form's
@@ -309,9 +298,8 @@ CML_API long long cml_gmm_lds(int dp, int k) {
 CML_API int cml_gmm_grid(long long n, int dp, int k, int ncu, int predict) {
   const long long lds = cml_gmm_lds(dp, k);
   if (lds == 0 || n <= 0) return 0;
-  const long long tr = 2048 / dp, tiles = (n + tr - 1) / tr;
-  const long long cap = (long long)(ncu > 0 ? ncu : 256) * (predict && lds <= 80 * 1024 ? 2 : 1);
-  return (int)(tiles < cap ? tiles : cap);
+  const long long tr = 2048 / dp;
+  return (int)cml_grid_cap((n + tr - 1) / tr, ncu, predict && lds <= kLdsPerCu / 2 ? 2 : 1);
 }
 
 // X: bf16 [n, dp] contiguous; wts f64 [n] or null; tab f64 [k dp dp | k dp | k] (A_j^T in 16-column blocks, mu
@@ -324,8 +312,7 @@ CML_API int cml_gmm_estep(const void* X, long long n, int dp, int d, int k, cons
   hipStream_t st = (hipStream_t)stream;
   const int rc = gm_launch_dp<false>(dp, grid, lds, st, X, n, d, k, wts, tab, part, nullptr, nullptr);
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(gmm_fold_kernel, dim3((unsigned)((ps + 255) / 256)), dim3(256), 0, st, part, grid, ps, out);
-  return cml_status();
+  return cml_launch_fold(gmm_fold_kernel, ps, st, part, grid, ps, out);
 }
 
 // prob f64 [n, k], label i32 [n].

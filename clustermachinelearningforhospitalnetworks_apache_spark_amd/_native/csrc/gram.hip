@@ -18,8 +18,7 @@
 // stored as 0, rows >= n get w = 0 and z = 0, so that pad columns (which may hold NaN bits) and rows past the
 // view never reach a product. z and w of the tile are staged as f64 side arrays. The global loads of a tile are
 // issued one tile ahead and wait in registers while the previous tile is computed (K30's scheme).
-// Operands follow the f64 MFMA layout of v_mfma_f64_16x16x4_f64 (lane l: A[row l & 15][k l >> 4],
-// B[k l >> 4][col l & 15]; result col = l & 15, row = (l >> 4) + 4 reg): for block (ti, tj) and K-step s both
+// Operands follow the f64 MFMA layout of v_mfma_f64_16x16x4_f64 (mfma64.h): for block (ti, tj) and K-step s both
 // operands are read at LDS row 4 s + (l >> 4), column 16 t + (l & 15); the B side is multiplied by w[row] in
 // f64 after the widening. The LDS pitch is 128 + 16 bf16 = 72 dwords, so the four row groups of a wave read
 // banks 8 dwords apart (16 lanes of a group cover 8 dwords): no conflict.
@@ -30,7 +29,7 @@
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): gram_pass_kernel
 // 216 VGPRs (of them 128 accumulators) at __launch_bounds__(256, 2), no scratch, 37 888 B LDS (two panels
 // 2 * 64 * 144 * 2 B + z and w 2 * 64 * 8 B): two workgroups per CU. gram_fold_kernel: no LDS, no scratch.
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
@@ -41,15 +40,12 @@ constexpr int kGrXP = kGrPanel + 16;   // bf16 pitch of a staged row
 constexpr int kGrSlots = 64;           // block slots of a workgroup: 16 per wave
 constexpr int kGrMaxD = 512;
 constexpr int kGrMinD = 31;
-typedef double gr_f64x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int gr_tiles(int d) { return (d + 15) / 16; }
 __host__ __device__ constexpr int gr_panels(int d) { return (gr_tiles(d) + 7) / 8; }
 __host__ __device__ constexpr int gr_pairs(int d) { return gr_panels(d) * (gr_panels(d) + 1) / 2; }
 // index of panel pair (p <= q) among np panels, rows of the upper triangle in order
 __host__ __device__ constexpr int gr_pair_index(int p, int q, int np) { return p * np - p * (p - 1) / 2 + (q - p); }
-
-__device__ __forceinline__ double gr_bf16(u16 v) { return (double)__uint_as_float(((unsigned)v) << 16); }
 
 __global__ __launch_bounds__(kGrThreads, 2) void gram_pass_kernel(
     const u16* __restrict__ X, long long n, long long ldx, int wc, int d, const double* __restrict__ z,
@@ -86,12 +82,13 @@ __global__ __launch_bounds__(kGrThreads, 2) void gram_pass_kernel(
       }
   }
 
-  gr_f64x4 acc[16];
+  f64x4 acc[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = (gr_f64x4)0.0;
+  for (int i = 0; i < 16; ++i) acc[i] = (f64x4)0.0;
 
   const long long ntiles = (n + kGrTile - 1) / kGrTile;
-  const long long t0 = ntiles * slab / nslabs, t1 = ntiles * (slab + 1) / nslabs;
+  long long t0, t1;
+  tile_run(ntiles, slab, nslabs, t0, t1);
 
   // One item = 8 bf16 of one row (16 bytes); a thread holds its 4 items per panel of a tile in registers. The loads
   // of tile + 1 are issued before the products of tile. wc is a multiple of 8, so a chunk is inside the row or not.
@@ -157,7 +154,7 @@ __global__ __launch_bounds__(kGrThreads, 2) void gram_pass_kernel(
 #pragma unroll
         for (int t = 0; t < 8; ++t)
           if (live & (1u << t))
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(gr_bf16(Xs[0][row][16 * t + c]), ub, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)bf16_to_f32(Xs[0][row][16 * t + c]), ub, acc[t], 0, 0, 0);
         acc[8] = __builtin_amdgcn_mfma_f64_16x16x4f64(u, ub, acc[8], 0, 0, 0);
       }
     } else if (live) {
@@ -168,8 +165,8 @@ __global__ __launch_bounds__(kGrThreads, 2) void gram_pass_kernel(
         double a[4], b[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          a[i] = gr_bf16(Xs[0][row][16 * (4 * ai + i) + c]);
-          b[i] = wv * gr_bf16(Xs[sb][row][16 * (4 * bj + i) + c]);
+          a[i] = (double)bf16_to_f32(Xs[0][row][16 * (4 * ai + i) + c]);
+          b[i] = wv * (double)bf16_to_f32(Xs[sb][row][16 * (4 * bj + i) + c]);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -257,10 +254,7 @@ CML_API int cml_gram_mfma(const void* X, long long n, long long ldx, int wc, int
   const int npairs = gr_pairs(d);
   hipLaunchKernelGGL(gram_pass_kernel, dim3((unsigned)(slabs * npairs)), dim3(kGrThreads), 0, st, (const u16*)X, n, ldx,
                      wc, d, z, w, part, npairs);
-  int rc = cml_status();
+  const int rc = cml_status();
   if (rc != 0) return rc;
-  const long long ne = (long long)(d + 2) * (d + 2);
-  hipLaunchKernelGGL(gram_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, part, slabs, npairs, d,
-                     out);
-  return cml_status();
+  return cml_launch_fold(gram_fold_kernel, (long long)(d + 2) * (d + 2), st, part, slabs, npairs, d, out);
 }

@@ -14,8 +14,8 @@
 //            are stored in the order the sweeps read them: position 4 g + r holds term g + 4 r, so that lane
 //            group g reads its four values with one 8-byte load.
 //   phase A  a wave owns 16 documents, document = lane & 15, lane group g = lane >> 4, and sweeps them to
-//            convergence on v_mfma_f64_16x16x4_f64 (lane l: A[row l&15][k l>>4], B[k l>>4][col l&15]; results
-//            col = l&15, row = (l>>4) + 4 reg). Per 16-term block: phinorm^T[term][doc] = beta^T e^T with the
+//            convergence on v_mfma_f64_16x16x4_f64 (operand layout: mfma64.h). Per 16-term block:
+//            phinorm^T[term][doc] = beta^T e^T with the
 //            lane's e_j (topics g + 4 s) as B; Q = x / phinorm in the accumulator registers, whose register r
 //            holds term g + 4 r: exactly the B operand of K-step r of acc[topic][doc] += beta[topic][term] Q^T.
 //            acc leaves gamma' with topics g + 4 r on the lane, again in B-operand order. Up to four term blocks
@@ -36,14 +36,13 @@
 // f(topic) = 2 (topic & 15) ^ 16 (topic & 1): in the first pattern the two topics of a half wave (g = 0, 1 or
 // 2, 3) differ in bit 4 of f and the 16 terms fill the low four bits; in the second the 16 topics give 16
 // distinct even f (bits 1..4 are topic bits 0, 1, 2 and 3 ^ 0) and the two terms g, g + 1 differ in bit 0.
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
 constexpr int kLdThreads = 256;
 constexpr int kLdTile = 64;  // documents per tile: 16 per wave
 constexpr int kLdMaxSweeps = 1000;
-typedef double ld_f64x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int ld_kp(int k) { return k <= 16 ? 16 : 32; }
 __host__ __device__ constexpr int ld_bp(int dp) { return dp < 32 ? 32 : dp; }  // f64 pitch of a beta row
@@ -57,7 +56,7 @@ __host__ __device__ constexpr long long ld_lds_bytes(int dp, int k) {
 __host__ __device__ constexpr bool ld_supported(int dp, int k) {
   if (dp < 16 || dp > 512 || (dp & (dp - 1)) != 0 || k < 2 || k > 32) return false;
   if (k > 16 && dp > 256) return false;
-  return ld_lds_bytes(dp, k) <= 160 * 1024;
+  return ld_lds_bytes(dp, k) <= kLdsPerCu;
 }
 
 // psi(x) for x > 0: the recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 10, two steps per division
@@ -74,10 +73,6 @@ __device__ __forceinline__ double ld_digamma(double x) {
   const double p = r2 * (1.0 / 12.0 - r2 * (1.0 / 120.0 - r2 * (1.0 / 252.0 - r2 * (1.0 / 240.0 - r2 * (1.0 / 132.0 -
                    r2 * (691.0 / 32760.0))))));
   return log(x) - 0.5 * r - p - s;
-}
-
-__device__ __forceinline__ double ld_bf16(unsigned bits16_in_high_half) {
-  return (double)__uint_as_float(bits16_in_high_half);
 }
 
 // Two workgroups share a CU (two waves per SIMD, one hiding the other's VALU and LDS latency) where two LDS images
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
   u16* Xs = reinterpret_cast<u16*>(red + 4 * KP);     // [64][XP]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
 
-  auto bsw = [](int topic, int term) { return topic * BP + (term ^ ((2 * (topic & 15)) ^ (16 * (topic & 1)))); };
+  auto bsw = [](int topic, int term) { return topic * BP + unit_swizzle(topic, term); };
 
   for (int i = tid; i < KP * DP; i += kLdThreads) beta[bsw(i / DP, i % DP)] = tab[i];
   if (tid < KP) al[tid] = alpha_g[tid];
@@ -119,21 +114,22 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
   double a_i[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    topic_of[i] = 16 * (i >> 2) + g + 4 * (i & 3);
+    topic_of[i] = unit_of_lane(i, g);
     real[i] = topic_of[i] < k;
   }
 
-  ld_f64x4 ss[NBW][KT];
+  f64x4 ss[NBW][KT];
 #pragma unroll
   for (int s = 0; s < NBW; ++s)
 #pragma unroll
-    for (int t = 0; t < KT; ++t) ss[s][t] = (ld_f64x4)0.0;
+    for (int t = 0; t < KT; ++t) ss[s][t] = (f64x4)0.0;
   double lph[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) lph[i] = 0.0;
 
   const long long ntiles = (B + kLdTile - 1) / kLdTile;
-  const long long t0 = ntiles * blockIdx.x / gridDim.x, t1 = ntiles * (blockIdx.x + 1) / gridDim.x;
+  long long t0, t1;
+  tile_run(ntiles, t0, t1);
   const double inv_k = 1.0 / (double)k;
 
   for (long long tile = t0; tile < t1; ++tile) {
@@ -151,6 +147,7 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
           hi = p[1];
         }
       }
+      // the same block as in mlp.hip and fm.hip: as a shared function it compiles to other machine code
       const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
       unsigned v[16];
 #pragma unroll
@@ -177,9 +174,7 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
       double sg = 0.0;
 #pragma unroll
       for (int i = 0; i < NI; ++i) sg += real[i] ? gam[i] : 0.0;
-      sg += __shfl_xor(sg, 16, 64);
-      sg += __shfl_xor(sg, 32, 64);
-      const double ps = ld_digamma(sg);
+      const double ps = ld_digamma(lane_groups_sum(sg));
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         el[i] = real[i] ? ld_digamma(gam[i]) - ps : 0.0;
@@ -192,16 +187,16 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
     const u16* xrow = Xs + (wave * 16 + c) * XP + 4 * g;
     for (int it = 0; it < kLdMaxSweeps; ++it) {
       if (__ballot(active) == 0ull) break;
-      ld_f64x4 acc[U][KT];
+      f64x4 acc[U][KT];
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int t = 0; t < KT; ++t) acc[u][t] = (ld_f64x4)0.0;
+        for (int t = 0; t < KT; ++t) acc[u][t] = (f64x4)0.0;
 #pragma unroll 1
       for (int tb0 = 0; tb0 < NB; tb0 += U) {
-        ld_f64x4 D[U];
+        f64x4 D[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) D[u] = (ld_f64x4)0.0;
+        for (int u = 0; u < U; ++u) D[u] = (f64x4)0.0;
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -211,10 +206,10 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const uint2 xv = *reinterpret_cast<const uint2*>(xrow + 16 * (tb0 + u));
-          D[u][0] = ld_bf16(xv.x << 16) / (D[u][0] + 1e-100);
-          D[u][1] = ld_bf16(xv.x & 0xffff0000u) / (D[u][1] + 1e-100);
-          D[u][2] = ld_bf16(xv.y << 16) / (D[u][2] + 1e-100);
-          D[u][3] = ld_bf16(xv.y & 0xffff0000u) / (D[u][3] + 1e-100);
+          D[u][0] = bf16hi_to_f64(xv.x << 16) / (D[u][0] + 1e-100);
+          D[u][1] = bf16hi_to_f64(xv.x & 0xffff0000u) / (D[u][1] + 1e-100);
+          D[u][2] = bf16hi_to_f64(xv.y << 16) / (D[u][2] + 1e-100);
+          D[u][3] = bf16hi_to_f64(xv.y & 0xffff0000u) / (D[u][3] + 1e-100);
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -234,9 +229,7 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
         ng[i] = et[i] * a + a_i[i];
         ch += real[i] ? fabs(ng[i] - gam[i]) : 0.0;
       }
-      ch += __shfl_xor(ch, 16, 64);
-      ch += __shfl_xor(ch, 32, 64);
-      ch *= inv_k;
+      ch = lane_groups_sum(ch) * inv_k;
       if (active) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) gam[i] = real[i] ? ng[i] : 1.0;
@@ -264,9 +257,9 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
       for (int slot = 0; slot < NBW; ++slot) {
         const int tb = wave + 4 * slot;
         if (tb < NB) {
-          ld_f64x4 D[4];
+          f64x4 D[4];
 #pragma unroll
-          for (int dg = 0; dg < 4; ++dg) D[dg] = (ld_f64x4)0.0;
+          for (int dg = 0; dg < 4; ++dg) D[dg] = (f64x4)0.0;
 #pragma unroll
           for (int i = 0; i < NI; ++i) {
             const double b = beta[bsw(topic_of[i], 16 * tb + c)];
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(kLdThreads, ld_wgs_per_cu(DP, 16 * KT)) void lda_es
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const unsigned xb = Xs[(16 * dg + g + 4 * r) * XP + xpos];
-              D[dg][r] = ld_bf16(xb << 16) / (D[dg][r] + 1e-100);
+              D[dg][r] = bf16hi_to_f64(xb << 16) / (D[dg][r] + 1e-100);
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s)
@@ -345,14 +338,8 @@ int ld_launch(int grid, hipStream_t st, const void* X, long long n, int d, int k
   if constexpr (!ld_supported(DP, 16 * KT)) {
     return (int)hipErrorInvalidValue;
   } else {
-    const long long lds = ld_lds_bytes(DP, 16 * KT);
-    // raise the dynamic LDS limit first; a failure of that call is this launch's error
-    const hipError_t e = hipFuncSetAttribute((const void*)lda_estep_kernel<DP, KT>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((lda_estep_kernel<DP, KT>), dim3((unsigned)grid), dim3(kLdThreads), (size_t)lds, st,
-                       (const u16*)X, n, d, k, rows, B, tab, alpha, gamma0, gamma, sweeps, part, fit);
-    return cml_status();
+    return cml_launch_lds(lda_estep_kernel<DP, KT>, grid, kLdThreads, ld_lds_bytes(DP, 16 * KT), st, (const u16*)X, n, d,
+                          k, rows, B, tab, alpha, gamma0, gamma, sweeps, part, fit);
   }
 }
 
@@ -378,9 +365,7 @@ CML_API long long cml_lda_lds(int dp, int k) { return ld_supported(dp, k) ? ld_l
 // CU, two where two LDS images fit.
 CML_API int cml_lda_grid(long long B, int dp, int k, int ncu) {
   if (!ld_supported(dp, k) || B <= 0) return 0;
-  const long long tiles = (B + kLdTile - 1) / kLdTile;
-  const long long cap = (long long)(ncu > 0 ? ncu : 256) * ld_wgs_per_cu(dp, ld_kp(k));
-  return (int)(tiles < cap ? tiles : cap);
+  return (int)cml_grid_cap((B + kLdTile - 1) / kLdTile, ncu, ld_wgs_per_cu(dp, ld_kp(k)));
 }
 
 // X: bf16 [n, dp] contiguous; rows: i64 [B] (indices into X; one outside [0, n) reads as an empty document) or
@@ -399,15 +384,11 @@ CML_API int cml_lda_estep(const void* X, long long n, int dp, int d, int k, cons
                          : ld_launch_dp<2>(dp, grid, st, X, n, d, k, rows, B, tab, alpha, gamma0, gamma, sweeps, part, fit);
   if (rc != 0 || !fit) return rc;
   const long long ne = (long long)k * d + k;
-  hipLaunchKernelGGL(lda_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, part, grid, ld_kp(k), dp, k,
-                     d, out);
-  return cml_status();
+  return cml_launch_fold(lda_fold_kernel, ne, st, part, grid, ld_kp(k), dp, k, d, out);
 }
 
 // out[i] = the kernel's psi(in[i]), f64.
 CML_API int cml_lda_digamma(const double* in, double* out, long long n, void* stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(lda_digamma_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out,
-                     n);
-  return cml_status();
+  return cml_launch_fold(lda_digamma_kernel, n, (hipStream_t)stream, in, out, n);
 }

@@ -15,8 +15,8 @@
 //             with one 8-byte load (K29's order). The global loads of a tile are issued one tile ahead and wait
 //             in registers while the previous tile is computed.
 //   forward   a wave owns 16 rows, row = lane & 15, lane group g = lane >> 4, transposed on
-//             v_mfma_f64_16x16x4_f64 (lane l: A[row l&15][k l>>4], B[k l>>4][col l&15]; results col = l&15,
-//             row = (l>>4) + 4 reg): Z^T[unit][row] = W[unit][k] A^T[k][row]. Accumulator register r of unit tile
+//             v_mfma_f64_16x16x4_f64 (operand layout: mfma64.h): Z^T[unit][row] = W[unit][k] A^T[k][row].
+//             Accumulator register r of unit tile
 //             t holds unit 16 t + g + 4 r, which is the B operand of K-step (t, r) of the next layer. Sigmoid, exp
 //             and log are f64 VALU; the softmax sums over a row's classes are sums over the four lane groups; pad
 //             classes are left out of it; rows past n get delta = 0 and no loss.
@@ -34,14 +34,13 @@
 // column index with f(unit) = 2 (unit & 15) ^ 16 (unit & 1) (lanes along units with lane groups along columns is
 // the only pattern it is read in; the swizzle also serves lanes along columns); the upper layers have pitch
 // HP + 2 (2 c + g), in both orientations; the staging buffers have pitch 66 (2 c + g).
-#include "common.h"
+#include "mfma64.h"
 
 namespace {
 
 constexpr int kMlThreads = 256;
 constexpr int kMlTile = 64;   // rows per tile: 16 per wave
 constexpr int kMlSP = 66;     // f64 pitch of a staging row (64 rows of a tile)
-typedef double ml_f64x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int ml_dpt(int dp) { return dp < 64 ? 64 : dp; }  // compiled width class
 
@@ -55,16 +54,12 @@ __host__ __device__ constexpr long long ml_lds_bytes(int dpt, int t, int nl) {
 
 __host__ __device__ constexpr bool ml_supported(int dp, int t, int nl) {
   if (dp < 16 || dp > 512 || (dp & (dp - 1)) != 0 || t < 1 || t > 2 || nl < 2 || nl > 3) return false;
-  return ml_lds_bytes(ml_dpt(dp), t, nl) <= 160 * 1024;
+  return ml_lds_bytes(ml_dpt(dp), t, nl) <= kLdsPerCu;
 }
 
 __host__ __device__ constexpr long long ml_part_len(int dp, int t, int nl) {
   const int hp = 16 * t;
   return (long long)hp * dp + (nl - 1) * hp * hp + nl * hp + 1;
-}
-
-__device__ __forceinline__ double ml_bf16(unsigned bits16_in_high_half) {
-  return (double)__uint_as_float(bits16_in_high_half);
 }
 
 template <int DPT, int T, int NL>
@@ -92,7 +87,7 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
   const int nb = dp >> 4;               // 16-column blocks of a row
 
-  auto wsw = [](int unit, int col) { return unit * BP + (col ^ ((2 * (unit & 15)) ^ (16 * (unit & 1)))); };
+  auto wsw = [](int unit, int col) { return unit * BP + unit_swizzle(unit, col); };
 
   for (int i = tid; i < HP * dp; i += kMlThreads) W1s[wsw(i / dp, i % dp)] = wp[i];
   const double* wu_g = wp + (long long)HP * dp;
@@ -108,16 +103,16 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
   bool real[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    unit_of[i] = 16 * (i >> 2) + g + 4 * (i & 3);
+    unit_of[i] = unit_of_lane(i, g);
     real[i] = unit_of[i] < C;
   }
 
-  ml_f64x4 g1[NBW];
+  f64x4 g1[NBW];
 #pragma unroll
-  for (int s = 0; s < NBW; ++s) g1[s] = (ml_f64x4)0.0;
-  ml_f64x4 gu[NL - 1];
+  for (int s = 0; s < NBW; ++s) g1[s] = (f64x4)0.0;
+  f64x4 gu[NL - 1];
 #pragma unroll
-  for (int l = 0; l < NL - 1; ++l) gu[l] = (ml_f64x4)0.0;
+  for (int l = 0; l < NL - 1; ++l) gu[l] = (f64x4)0.0;
   double dbacc[NL][NI];
 #pragma unroll
   for (int l = 0; l < NL; ++l)
@@ -126,7 +121,8 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
   double lossacc = 0.0;
 
   const long long ntiles = (n + kMlTile - 1) / kMlTile;
-  const long long t0 = ntiles * blockIdx.x / gridDim.x, t1 = ntiles * (blockIdx.x + 1) / gridDim.x;
+  long long t0, t1;
+  tile_run(ntiles, t0, t1);
 
   // One item = one 16-column block of one row (32 bytes); a thread holds its NIT items of a tile in registers.
   // The loads of tile + 1 are issued before the products of tile, so that no tile waits for HBM.
@@ -156,6 +152,7 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
       const int item = tid + kMlThreads * j;
       if (item < kMlTile * nb) {
         const int row = item >> lnb, tb = item & (nb - 1);
+        // the same block as in lda.hip and fm.hip: as a shared function it compiles to other machine code
         const unsigned w[8] = {pf[j][0].x, pf[j][0].y, pf[j][0].z, pf[j][0].w,
                                pf[j][1].x, pf[j][1].y, pf[j][1].z, pf[j][1].w};
         unsigned v[16];
@@ -179,18 +176,18 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
     if (tile + 1 < t1) fetch(tile + 1);
     double act[NL - 1][NI], cur[NI];
     {
-      ml_f64x4 z[2][T];  // two chains of column blocks
+      f64x4 z[2][T];  // two chains of column blocks
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        z[1][t] = (ml_f64x4)0.0;
+        z[1][t] = (f64x4)0.0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) z[0][t][r] = bs[16 * t + g + 4 * r];
       }
       const u16* xrow = Xs + (wave * 16 + c) * XP + 4 * g;
       auto block = [&](int tb, int u) {
         const uint2 xv = *reinterpret_cast<const uint2*>(xrow + 16 * tb);
-        const double xs[4] = {ml_bf16(xv.x << 16), ml_bf16(xv.x & 0xffff0000u), ml_bf16(xv.y << 16),
-                              ml_bf16(xv.y & 0xffff0000u)};
+        const double xs[4] = {bf16hi_to_f64(xv.x << 16), bf16hi_to_f64(xv.x & 0xffff0000u), bf16hi_to_f64(xv.y << 16),
+                              bf16hi_to_f64(xv.y & 0xffff0000u)};
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -216,7 +213,7 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
     }
 #pragma unroll
     for (int l = 1; l < NL; ++l) {
-      ml_f64x4 acc[T];
+      f64x4 acc[T];
 #pragma unroll
       for (int t = 0; t < T; ++t)
 #pragma unroll
@@ -258,10 +255,8 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
         s += e[i];
         zy += unit_of[i] == yv ? cur[i] : 0.0;
       }
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      zy += __shfl_xor(zy, 16, 64);
-      zy += __shfl_xor(zy, 32, 64);
+      s = lane_groups_sum(s);
+      zy = lane_groups_sum(zy);
       const double inv = 1.0 / s;
 #pragma unroll
       for (int i = 0; i < NI; ++i)
@@ -271,9 +266,9 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
     // ---- backward: delta of the hidden layers
 #pragma unroll
     for (int l = NL - 1; l >= 1; --l) {
-      ml_f64x4 acc[T];
+      f64x4 acc[T];
 #pragma unroll
-      for (int t = 0; t < T; ++t) acc[t] = (ml_f64x4)0.0;
+      for (int t = 0; t < T; ++t) acc[t] = (f64x4)0.0;
 #pragma unroll
       for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -319,7 +314,7 @@ __global__ __launch_bounds__(kMlThreads, 1) void mlp_pass_kernel(
             const u16* xb = Xs + g * XP + 16 * tb + 4 * (c & 3) + (c >> 2);
 #pragma unroll
             for (int s = 0; s < 16; ++s)
-              g1[slot] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[4 * s], ml_bf16((unsigned)xb[4 * s * XP] << 16),
+              g1[slot] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[4 * s], bf16hi_to_f64((unsigned)xb[4 * s * XP] << 16),
                                                               g1[slot], 0, 0, 0);
           }
         }
@@ -405,14 +400,8 @@ int ml_launch(int grid, hipStream_t st, const void* X, long long n, int dp, int 
   if constexpr (!ml_supported(DPT, T, NL)) {
     return (int)hipErrorInvalidValue;
   } else {
-    const long long lds = ml_lds_bytes(DPT, T, NL);
-    // raise the dynamic LDS limit first; a failure of that call is this launch's error
-    const hipError_t e = hipFuncSetAttribute((const void*)mlp_pass_kernel<DPT, T, NL>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((mlp_pass_kernel<DPT, T, NL>), dim3((unsigned)grid), dim3(kMlThreads), (size_t)lds, st,
-                       (const u16*)X, n, dp, d, C, y, wp, part, zout, fit);
-    return cml_status();
+    return cml_launch_lds(mlp_pass_kernel<DPT, T, NL>, grid, kMlThreads, ml_lds_bytes(DPT, T, NL), st, (const u16*)X, n,
+                          dp, d, C, y, wp, part, zout, fit);
   }
 }
 
@@ -439,9 +428,7 @@ CML_API long long cml_mlp_lds(int dp, int hmax, int nl) {
 // Workgroups of a launch: a function of (n, CUs) only for a supported shape, one per CU. 0 = unsupported or no row.
 CML_API int cml_mlp_grid(long long n, int dp, int hmax, int nl, int ncu) {
   if (cml_mlp_lds(dp, hmax, nl) == 0 || n <= 0) return 0;
-  const long long tiles = (n + kMlTile - 1) / kMlTile;
-  const long long cap = ncu > 0 ? ncu : 256;
-  return (int)(tiles < cap ? tiles : cap);
+  return (int)cml_grid_cap((n + kMlTile - 1) / kMlTile, ncu, 1);
 }
 
 // X: bf16 [n, dp] contiguous; layers = [d, s1, s2(, s3)] with nl = 2 or 3 weight layers (s3 = 0 at nl = 2); y: i32 [n]
@@ -470,7 +457,5 @@ CML_API int cml_mlp_pass(const void* X, long long n, int dp, int d, int nl, int 
   long long ne = 1;
   const int sz[4] = {d, s1, s2, s3};
   for (int l = 0; l < nl; ++l) ne += (long long)sz[l] * sz[l + 1] + sz[l + 1];
-  hipLaunchKernelGGL(mlp_fold_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, part, grid, 16 * t, dp, nl, d,
-                     s1, s2, s3, out);
-  return cml_status();
+  return cml_launch_fold(mlp_fold_kernel, ne, st, part, grid, 16 * t, dp, nl, d, s1, s2, s3, out);
 }

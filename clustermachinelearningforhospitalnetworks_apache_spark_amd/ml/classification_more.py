@@ -27,6 +27,7 @@ import torch
 
 from ..models.optim import lbfgs
 from ..ops import glm_ops
+from ..ops._fused import use_kernel
 from ..sql import types as T
 from ..sql.column import ColumnData
 from . import util as U
@@ -381,13 +382,6 @@ def _low_precision(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
 
 
-def _use_kernel(x: torch.Tensor, layers: List[int]) -> bool:
-    from ..ops import mlp_ops as MO
-    from ..utils.device import padded_dim
-    return (x.dtype == torch.bfloat16 and MO.kernel_enabled()
-            and MO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), layers))
-
-
 class MultilayerPerceptronClassifier(Estimator):
     """Feed-forward network: sigmoid hidden layers, softmax output with cross-entropy loss, trained
     full-batch (L-BFGS or gradient descent); weights initialised uniformly in ±sqrt(6/(in+out))
@@ -433,7 +427,7 @@ class MultilayerPerceptronClassifier(Estimator):
         if lowp:
             # the rows as they are: K30 on bf16 rows inside its limits, the chunked reference form otherwise
             from ..ops import mlp_ops as MO
-            kernel = _use_kernel(x, layers)
+            kernel = use_kernel(MO, x, layers)
             if kernel:
                 from ..models.kmeans import to_device_matrix
                 x = to_device_matrix(x, layers[0])  # a copy only when the layout is not already the kernel's
@@ -517,7 +511,7 @@ class MultilayerPerceptronClassificationModel(Model):
             if d != self._layers[0]:
                 raise ValueError(f"MultilayerPerceptronClassificationModel: input layer {self._layers[0]} != "
                                  f"feature size {d}")
-            if _use_kernel(x, self._layers):
+            if use_kernel(MO, x, self._layers):
                 from ..models.kmeans import to_device_matrix
                 return MO.forward(to_device_matrix(x, d), d, self._layers, p)
             return MO.forward_reference(x, d, self._layers, p)

@@ -30,6 +30,7 @@ import torch
 
 from ..sql import types as T
 from ..sql.column import ColumnData
+from ..ops._fused import use_kernel
 from . import util as U
 from .base import Estimator, Model
 from .feature import _replace_col
@@ -67,13 +68,6 @@ def _fm_scores(x: torch.Tensor, b, w, V) -> torch.Tensor:
 def _low_precision(x: torch.Tensor) -> bool:
     """bf16 and e4m3 device columns: the path without an f64 copy. Every other column keeps the dense form."""
     return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
-
-
-def _use_kernel(x: torch.Tensor, f: int) -> bool:
-    from ..ops import fm_ops as FO
-    from ..utils.device import padded_dim
-    return (x.dtype == torch.bfloat16 and FO.kernel_enabled()
-            and FO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), f))
 
 
 class _FMBase(Estimator):
@@ -115,7 +109,7 @@ class _FMBase(Estimator):
         if lowp:
             # the rows as they are: K32 on bf16 rows inside its limits, the chunked reference form otherwise
             from ..ops import fm_ops as FO
-            kernel = _use_kernel(x, f)
+            kernel = use_kernel(FO, x, f)
             if kernel:
                 from ..models.kmeans import to_device_matrix
                 x = to_device_matrix(x, d)  # a copy only when the layout is not already the kernel's
@@ -207,7 +201,7 @@ class _FMModelBase(Model):
             if d != self._w.size:
                 raise ValueError(f"{type(self).__name__}: {self._w.size} features fitted, the column has {d}")
             p = torch.as_tensor(np.concatenate([[self._b], self._w, self._V.reshape(-1)]), device=dev)
-            if _use_kernel(x, f):
+            if use_kernel(FO, x, f):
                 from ..models.kmeans import to_device_matrix
                 return FO.scores(to_device_matrix(x, d), d, p, f)
             return FO.scores_reference(x, d, p, f)

@@ -26,6 +26,7 @@ import torch
 
 from ..sql import types as T
 from ..sql.column import ColumnData
+from ..ops._fused import use_kernel
 from . import util as U
 from .base import Estimator, Model
 from .feature import _replace_col
@@ -94,13 +95,6 @@ def _estep_tables(weights: np.ndarray, covs: np.ndarray):
 def _low_precision(x: torch.Tensor) -> bool:
     """bf16 and e4m3 device columns: the path without an f64 copy. Every other column keeps the dense form."""
     return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
-
-
-def _use_kernel(x: torch.Tensor, k: int) -> bool:
-    from ..ops import gmm_ops as GO
-    from ..utils.device import padded_dim
-    return (x.dtype == torch.bfloat16 and GO.kernel_enabled()
-            and GO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), k))
 
 
 def _m_step(o: np.ndarray, k: int, d: int):
@@ -210,7 +204,7 @@ class GaussianMixture(Estimator):
         from ..ops import gmm_ops as GO
         d = int(x.shape[1])
         comm = df._comm
-        kernel = _use_kernel(x, k)
+        kernel = use_kernel(GO, x, k)
         weights, mus, covs = self._init(df, x, w, k, seed, lowp=True)
         if kernel:
             from ..models.kmeans import to_device_matrix
@@ -268,7 +262,7 @@ class GaussianMixtureModel(Model):
         from ..ops import gmm_ops as GO
         d = int(x.shape[1])
         A, c = _estep_tables(self._w, self._cov)
-        if _use_kernel(x, len(self._w)):
+        if use_kernel(GO, x, len(self._w)):
             from ..models.kmeans import to_device_matrix
             return GO.predict(to_device_matrix(x, d), d, A, self._mu, c)
         return GO.predict_reference(x, d, None, A, self._mu, c)

@@ -31,6 +31,7 @@ import torch
 
 from ..sql import types as T
 from ..sql.column import ColumnData
+from ..ops._fused import use_kernel
 from ..utils import rng as R
 from . import util as U
 from .base import Estimator, Model
@@ -88,13 +89,6 @@ def _gamma_init(row_ids: torch.Tensor, k: int, seed: int) -> torch.Tensor:
 
 def _low_precision(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
-
-
-def _use_kernel(x: torch.Tensor, k: int) -> bool:
-    from ..ops import lda_ops as LO
-    from ..utils.device import padded_dim
-    return (x.dtype == torch.bfloat16 and LO.kernel_enabled()
-            and LO.kernel_supported(x.dtype, padded_dim(int(x.shape[1])), k))
 
 
 def _row_sums(X: torch.Tensor) -> torch.Tensor:
@@ -231,7 +225,7 @@ class LDA(Estimator):
         gen = np.random.default_rng(seed & 0xFFFFFFFF)
         lam = torch.as_tensor(gen.gamma(GAMMA_SHAPE, 1.0 / GAMMA_SHAPE, size=(k, V)), device=dev)
         tau0, kappa, frac = self.getLearningOffset(), self.getLearningDecay(), self.getSubsamplingRate()
-        kernel = _use_kernel(x, k)
+        kernel = use_kernel(LO, x, k)
         if kernel:
             from ..models.kmeans import to_device_matrix
             x = to_device_matrix(x, V)  # a copy only when the layout is not already the kernel's
@@ -392,7 +386,7 @@ class LocalLDAModel(Model):
             from ..ops import lda_ops as LO
             V = int(X.shape[1])
             gamma0 = _gamma_init(df._row_ids, k, self._gamma_seed)
-            if _use_kernel(X, k):
+            if use_kernel(LO, X, k):
                 from ..models.kmeans import to_device_matrix
                 gammas, _ = LO.infer(to_device_matrix(X, V), None, V, e_beta, alpha, gamma0)
             else:

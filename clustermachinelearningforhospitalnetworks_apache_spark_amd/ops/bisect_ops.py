@@ -20,7 +20,6 @@ nodes that span several units. ``CML_BISECT_KERNEL=0`` keeps the estimator on th
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -28,6 +27,7 @@ import torch
 from .. import _native
 from .._native import c_int, c_ll, c_vp
 from . import silhouette_ops as SO
+from ._fused import env_enabled
 
 _native.register_kernel_sigs({
     "cml_bisect_step": (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -39,7 +39,7 @@ M_MAX = 1 << 20  # nodes divided on one level (k - 1 at the most)
 
 
 def kernel_enabled() -> bool:
-    return os.environ.get("CML_BISECT_KERNEL", "1") != "0"
+    return env_enabled("CML_BISECT_KERNEL")
 
 
 def kernel_supported(dtype: torch.dtype, dp: int) -> bool:

@@ -24,13 +24,13 @@ reference form.
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 
 from .. import _native
 from .._native import c_int, c_ll, c_vp
+from ._fused import check_matrix, env_enabled, gather_rows, ncu, row_list, widen
 
 _native.register_kernel_sigs({
     "cml_fm_lds": (c_ll, [c_int, c_int]),
@@ -45,7 +45,7 @@ LOSSES = ("squared", "logistic")
 
 
 def kernel_enabled() -> bool:
-    return os.environ.get("CML_FM_KERNEL", "1") != "0"
+    return env_enabled("CML_FM_KERNEL")
 
 
 def size(d: int, f: int) -> int:
@@ -78,22 +78,6 @@ def kernel_supported(dtype: torch.dtype, dp: int, f: int) -> bool:
 
 
 # ---------------------------------------------------------------------------------------------- reference form
-def _widen(v: torch.Tensor) -> torch.Tensor:
-    if v.dtype == torch.float8_e4m3fn:
-        v = v.to(torch.float32)
-    return v.to(torch.float64)
-
-
-def _gather(x: torch.Tensor, idx: Optional[torch.Tensor], st: int, chunk: int, d: int) -> torch.Tensor:
-    """One chunk of the listed rows (None: of all rows), widened to f64 (e4m3 rows are gathered as bytes)."""
-    if idx is None:
-        return _widen(x[st:st + chunk, :d])
-    sel = idx[st:st + chunk]
-    if x.dtype == torch.float8_e4m3fn:
-        return _widen(x.view(torch.uint8)[sel].view(torch.float8_e4m3fn)[:, :d])
-    return _widen(x[sel][:, :d])
-
-
 def _params(x, d: int, p, f: int, what: str):
     d, f = int(d), int(f)
     if not torch.is_tensor(x) or x.dim() != 2 or d < 1 or x.shape[1] < d or f < 1:
@@ -102,14 +86,6 @@ def _params(x, d: int, p, f: int, what: str):
     if p.dim() != 1 or p.numel() != size(d, f):
         raise ValueError(f"{what}: {p.numel()} parameters, d = {d} and factor size {f} need {size(d, f)}")
     return p[0], p[1:1 + d], p[1 + d:].reshape(d, f)
-
-
-def _row_list(rows, n: int, dev, what: str) -> Optional[torch.Tensor]:
-    if rows is None:
-        return None
-    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1:
-        raise ValueError(f"{what}: the row list must be a 1-d int64 tensor")
-    return rows.to(dev).contiguous()
 
 
 def _scores_chunk(v, b, w, V, sv):
@@ -130,7 +106,8 @@ def loss_grad_reference(x: torch.Tensor, rows: Optional[torch.Tensor], d: int, y
     if not torch.is_tensor(y) or y.shape != (n,):
         raise ValueError(f"{what}: one label per row of x is expected")
     y = y.to(device=dev, dtype=torch.float64)
-    rows = _row_list(rows, n, dev, what)
+    if rows is not None:
+        rows = row_list(rows, dev, what)
     B = n if rows is None else int(rows.shape[0])
     sv = (V * V).sum(1)
     db = torch.zeros((), dtype=torch.float64, device=dev)
@@ -139,7 +116,7 @@ def loss_grad_reference(x: torch.Tensor, rows: Optional[torch.Tensor], d: int, y
     dV = torch.zeros(d, f, dtype=torch.float64, device=dev)
     total = torch.zeros((), dtype=torch.float64, device=dev)
     for st in range(0, B, chunk):
-        v = _gather(x, rows, st, chunk, d)
+        v = widen(x[st:st + chunk, :d]) if rows is None else gather_rows(x, rows[st:st + chunk], d)
         yc = y[st:st + chunk] if rows is None else y[rows[st:st + chunk]]
         t, s = _scores_chunk(v, b, w, V, sv)
         if loss == "logistic":
@@ -164,16 +141,11 @@ def scores_reference(x: torch.Tensor, d: int, p, f: int, chunk: int = CHUNK) -> 
     n = int(x.shape[0])
     out = torch.empty(n, dtype=torch.float64, device=x.device)
     for st in range(0, n, chunk):
-        out[st:st + chunk] = _scores_chunk(_widen(x[st:st + chunk, :d]), b, w, V, sv)[1]
+        out[st:st + chunk] = _scores_chunk(widen(x[st:st + chunk, :d]), b, w, V, sv)[1]
     return out
 
 
 # ---------------------------------------------------------------------------------------------------- kernel
-def _ncu(dev) -> int:
-    from ..utils.device import num_cus
-    return num_cus(dev.index if dev.index is not None else torch.cuda.current_device())
-
-
 def _pack(p: torch.Tensor, d: int, f: int, dp: int) -> torch.Tensor:
     """The kernel's parameter image: ``[hp, dp]`` with rows 0 .. f - 1 = V^T and row f = w, zero padded, then b."""
     hp = 16 if f <= 15 else 32
@@ -189,9 +161,8 @@ def _launch(xd, rows, d, y, p, f, loss, fit: bool, what: str):
     if not torch.is_tensor(xd) or xd.dim() != 2:
         raise ValueError(f"{what}: rows must be a 2-d tensor")
     dp, d, f = int(xd.shape[1]), int(d), int(f)
-    if (not xd.is_cuda or not xd.is_contiguous() or not kernel_supported(xd.dtype, dp, f) or not 1 <= d <= dp):
-        raise ValueError(f"{what}: rows must be a contiguous bf16 device matrix of padded width 16..512 and the "
-                         "factor size inside the kernel's limits")
+    check_matrix(xd, d, lambda dtype, dp: kernel_supported(dtype, dp, f), what,
+                 "16..512 and the factor size inside the kernel's limits")
     n, dev = int(xd.shape[0]), xd.device
     p = torch.as_tensor(p)
     if p.dim() != 1 or p.numel() != size(d, f):
@@ -202,19 +173,20 @@ def _launch(xd, rows, d, y, p, f, loss, fit: bool, what: str):
         if (not torch.is_tensor(y) or y.dtype != torch.float64 or y.shape != (n,) or y.device != dev
                 or not y.is_contiguous()):
             raise ValueError(f"{what}: the labels must be a contiguous f64 device vector, one per row of the matrix")
-        rows = _row_list(rows, n, dev, what)
+        if rows is not None:
+            rows = row_list(rows, dev, what)
     B = n if rows is None else int(rows.shape[0])
     out = torch.zeros(size(d, f) + 1, dtype=torch.float64, device=dev) if fit else torch.empty(
         n, dtype=torch.float64, device=dev)
     if B:
         hp = 16 if f <= 15 else 32
         wp = _pack(p.to(device=dev, dtype=torch.float64), d, f, dp)
-        lib, ncu = _native.kernels(), _ncu(dev)
-        grid = int(lib.cml_fm_grid(B, dp, f, ncu))
+        lib, cus = _native.kernels(), ncu(dev)
+        grid = int(lib.cml_fm_grid(B, dp, f, cus))
         part = torch.empty(grid * (hp * dp + dp + 2), dtype=torch.float64, device=dev) if fit else None
         _native.check(lib.cml_fm_pass(xd.data_ptr(), n, dp, d, f, _native.ptr(rows), B, _native.ptr(y if fit else None),
                                       wp.data_ptr(), _native.ptr(part), grid, out.data_ptr(), 1 if fit else 0,
-                                      1 if loss == "logistic" else 0, ncu,
+                                      1 if loss == "logistic" else 0, cus,
                                       torch.cuda.current_stream(dev).cuda_stream), what)
     return out
 

@@ -13,7 +13,7 @@ import torch
 
 from .. import _native
 from .._native import c_dbl, c_int, c_ll, c_vp
-from ..utils.device import num_cus
+from ._fused import ncu
 
 _native.register_kernel_sigs({
     "cml_glm_grid": (c_int, [c_ll, c_int, c_int, c_int, c_int]),
@@ -67,12 +67,12 @@ _UNROLL = [0]
 
 
 def _grid(n: int, d: int, code: int, dev, kind: str) -> int:
-    return _grid_cached(n, d, code, dev.index or 0, kind, _UNROLL[0])
+    return _grid_cached(n, d, code, ncu(dev), kind, _UNROLL[0])
 
 
 @functools.lru_cache(maxsize=256)
-def _grid_cached(n: int, d: int, code: int, dev_index: int, kind: str, unroll: int) -> int:
-    g = _native.kernels().cml_glm_grid(n, d, code, num_cus(dev_index), _KIND[kind])
+def _grid_cached(n: int, d: int, code: int, cus: int, kind: str, unroll: int) -> int:
+    g = _native.kernels().cml_glm_grid(n, d, code, cus, _KIND[kind])
     if g < 0:
         raise ValueError(f"feature width {d} too large for the GLM kernels")
     return g
@@ -248,7 +248,7 @@ def multinomial_grad(x: torch.Tensor, d: int, y: torch.Tensor, coef: torch.Tenso
             # 32 / 56 ms for the VALU kernel over 100M x 256, profiles/r6/multinomial_100Mx256_bf16.log)
             return _multinomial_mfma(xx, d, y, coef, weight, C, cp, int(k.cml_multinomial_mfma_dpad(d, C)))
         if k.cml_multinomial_supported(d, code, C) > 0:
-            g = k.cml_multinomial_grid(n, d, code, C, num_cus(xx.device.index or 0))
+            g = k.cml_multinomial_grid(n, d, code, C, ncu(xx.device))
             m = C * d + C + 2
             out = torch.empty((g, m), dtype=torch.float64, device=xx.device)
             yy = y.to(torch.float64).contiguous()
@@ -299,7 +299,7 @@ def multinomial_predict(x: torch.Tensor, d: int, coef: torch.Tensor):
     raw = torch.empty((n, C), dtype=torch.float64, device=x.device)
     prob = torch.empty((n, C), dtype=torch.float64, device=x.device)
     _native.check(k.cml_multinomial_predict(xx.data_ptr(), n, xx.stride(0), d, code, C, cf.data_ptr(), raw.data_ptr(),
-                                            prob.data_ptr(), num_cus(x.device.index or 0), _native.stream_ptr()),
+                                            prob.data_ptr(), ncu(x.device), _native.stream_ptr()),
                   "multinomial_predict")
     return raw, prob
 
@@ -317,7 +317,7 @@ def _multinomial_mfma(xx: torch.Tensor, d: int, y: torch.Tensor, coef: torch.Ten
     """K13m on MFMA (glm_mfma.hip) -> [∇W (C·d) | ∇b (C) | loss | weight sum], the layout of multinomial_grad."""
     n = int(xx.shape[0])
     k = _native.kernels()
-    g = k.cml_multinomial_mfma_grid(n, num_cus(xx.device.index or 0))
+    g = k.cml_multinomial_mfma_grid(n, ncu(xx.device))
     out = torch.empty((g, cp * dp + C + 2), dtype=torch.float64, device=xx.device)
     yy = y.to(torch.float64).contiguous()
     ww = weight.to(torch.float64).contiguous() if weight is not None else None
@@ -426,7 +426,7 @@ def gram(x: torch.Tensor, d: int, y: torch.Tensor, weight: Optional[torch.Tensor
     xx = x if x.dtype in _CODE else x.to(torch.float64)
     if xx.stride(1) != 1:
         xx = xx.contiguous()
-    grid = max(1, min((n + 2047) // 2048, num_cus(xx.device.index or 0) * 4))
+    grid = max(1, min((n + 2047) // 2048, ncu(xx.device) * 4))
     out = torch.zeros((grid, m * m), dtype=torch.float64, device=xx.device)
     yy = y.to(torch.float64).contiguous()
     ww = weight.to(torch.float64).contiguous() if weight is not None else None

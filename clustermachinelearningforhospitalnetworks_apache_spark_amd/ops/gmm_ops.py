@@ -20,7 +20,6 @@ the per-workgroup partials in workgroup order. ``CML_GMM_KERNEL=0`` keeps the es
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import numpy as np
@@ -28,6 +27,7 @@ import torch
 
 from .. import _native
 from .._native import c_int, c_ll, c_vp
+from ._fused import check_matrix, env_enabled, gather_rows, ncu, widen  # gather_rows: a public name here
 
 _native.register_kernel_sigs({
     "cml_gmm_lds": (c_ll, [c_int, c_int]),
@@ -40,7 +40,7 @@ CHUNK = 1 << 16
 
 
 def kernel_enabled() -> bool:
-    return os.environ.get("CML_GMM_KERNEL", "1") != "0"
+    return env_enabled("CML_GMM_KERNEL")
 
 
 def kernel_supported(dtype: torch.dtype, dp: int, k: int) -> bool:
@@ -54,12 +54,6 @@ def kernel_supported(dtype: torch.dtype, dp: int, k: int) -> bool:
 
 
 # ---------------------------------------------------------------------------------------------- reference form
-def _widen(v: torch.Tensor) -> torch.Tensor:
-    if v.dtype == torch.float8_e4m3fn:
-        v = v.to(torch.float32)
-    return v.to(torch.float64)
-
-
 def _params(A, mu, c, dev):
     A = torch.as_tensor(np.asarray(A, dtype=np.float64), device=dev)
     mu = torch.as_tensor(np.asarray(mu, dtype=np.float64), device=dev)
@@ -87,7 +81,7 @@ def estep_reference(x: torch.Tensor, d: int, weights: Optional[torch.Tensor], A,
     S2 = torch.zeros(k, d, d, dtype=torch.float64, device=dev)
     tail = torch.zeros(2, dtype=torch.float64, device=dev)
     for st in range(0, n, chunk):
-        v = _widen(x[st:st + chunk, :d])
+        v = widen(x[st:st + chunk, :d])
         lp = _chunk_lp(v, A, mu, c)
         lse = torch.logsumexp(lp, 1)
         r = torch.exp(lp - lse[:, None])
@@ -118,18 +112,11 @@ def predict_reference(x: torch.Tensor, d: int, weights: Optional[torch.Tensor], 
     label = torch.empty(n, dtype=torch.int32, device=dev)
     ar = torch.arange(k, device=dev)
     for st in range(0, n, chunk):
-        lp = _chunk_lp(_widen(x[st:st + chunk, :d]), A, mu, c)
+        lp = _chunk_lp(widen(x[st:st + chunk, :d]), A, mu, c)
         prob[st:st + chunk] = torch.exp(lp - torch.logsumexp(lp, 1)[:, None])
         top = lp == lp.max(1, keepdim=True).values
         label[st:st + chunk] = torch.where(top, ar, torch.full_like(ar, k)).min(1).values.to(torch.int32)
     return prob, label
-
-
-def gather_rows(x: torch.Tensor, idx: torch.Tensor, d: int) -> torch.Tensor:
-    """Rows ``idx`` of a column of any dtype, widened to f64 (e4m3 rows are gathered as bytes)."""
-    if x.dtype == torch.float8_e4m3fn:
-        return _widen(x.view(torch.uint8)[idx].view(torch.float8_e4m3fn)[:, :d])
-    return _widen(x[idx][:, :d])
 
 
 def column_moments(x: torch.Tensor, d: int, weights: Optional[torch.Tensor], chunk: int = CHUNK) -> torch.Tensor:
@@ -137,7 +124,7 @@ def column_moments(x: torch.Tensor, d: int, weights: Optional[torch.Tensor], chu
     dev = x.device
     out = torch.zeros(1 + 2 * d, dtype=torch.float64, device=dev)
     for st in range(0, int(x.shape[0]), chunk):
-        v = _widen(x[st:st + chunk, :d])
+        v = widen(x[st:st + chunk, :d])
         if weights is None:
             out[0] += float(v.shape[0])
             out[1:1 + d] += v.sum(0)
@@ -153,10 +140,8 @@ def column_moments(x: torch.Tensor, d: int, weights: Optional[torch.Tensor], chu
 
 # ---------------------------------------------------------------------------------------------------- kernel
 def _check(xd: torch.Tensor, d: int, k: int, what: str):
-    if (not xd.is_cuda or xd.dim() != 2 or not xd.is_contiguous()
-            or not kernel_supported(xd.dtype, int(xd.shape[1]), k) or not 1 <= d <= int(xd.shape[1])):
-        raise ValueError(f"{what}: rows must be a contiguous bf16 device matrix of padded width 16 or 32, "
-                         "with k inside the kernel's limits")
+    check_matrix(xd, d, lambda dtype, dp: kernel_supported(dtype, dp, k), what,
+                 "16 or 32, with k inside the kernel's limits")
 
 
 def _tables(A, mu, c, d: int, dp: int, dev) -> torch.Tensor:
@@ -176,11 +161,6 @@ def _tables(A, mu, c, d: int, dp: int, dev) -> torch.Tensor:
     return torch.as_tensor(np.concatenate([bt.reshape(-1), mp.reshape(-1), c]), device=dev)
 
 
-def _ncu(dev) -> int:
-    from ..utils.device import num_cus
-    return num_cus(dev.index if dev.index is not None else torch.cuda.current_device())
-
-
 def estep(xd: torch.Tensor, d: int, weights: Optional[torch.Tensor], A, mu, c):
     """K28, fit form: ``(stats, tail)`` as ``estep_reference`` returns them. All arithmetic after the exact
     bf16 -> f64 widening is f64 (the products on the f64 MFMA); pad columns are masked by ``d``. No atomics;
@@ -196,11 +176,11 @@ def estep(xd: torch.Tensor, d: int, weights: Optional[torch.Tensor], A, mu, c):
             if weights.shape[0] != n:
                 raise ValueError("gmm estep: the weights differ in length from the rows")
         tab = _tables(A, mu, c, d, dp, dev)
-        lib, ncu = _native.kernels(), _ncu(dev)
-        grid = int(lib.cml_gmm_grid(n, dp, k, ncu, 0))
+        lib, cus = _native.kernels(), ncu(dev)
+        grid = int(lib.cml_gmm_grid(n, dp, k, cus, 0))
         part = torch.empty(grid * (k * cs + 2), dtype=torch.float64, device=dev)
         _native.check(lib.cml_gmm_estep(xd.data_ptr(), n, dp, d, k, _native.ptr(weights), tab.data_ptr(),
-                                        part.data_ptr(), grid, out.data_ptr(), ncu,
+                                        part.data_ptr(), grid, out.data_ptr(), cus,
                                         torch.cuda.current_stream(dev).cuda_stream), "gmm_estep")
     return out[:k * cs].view(k, cs), out[k * cs:]
 
@@ -215,6 +195,6 @@ def predict(xd: torch.Tensor, d: int, A, mu, c):
     if n:
         tab = _tables(A, mu, c, d, dp, dev)
         _native.check(_native.kernels().cml_gmm_predict(xd.data_ptr(), n, dp, d, k, tab.data_ptr(),
-                                                        prob.data_ptr(), label.data_ptr(), _ncu(dev),
+                                                        prob.data_ptr(), label.data_ptr(), ncu(dev),
                                                         torch.cuda.current_stream(dev).cuda_stream), "gmm_predict")
     return prob, label

@@ -17,13 +17,13 @@ in slab order and mirrors. ``CML_GRAM_KERNEL=0`` keeps every such column on the 
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 
 from .. import _native
 from .._native import c_int, c_ll, c_vp
+from ._fused import env_enabled, ncu, widen
 
 _native.register_kernel_sigs({
     "cml_gram_mfma_slabs": (c_int, [c_ll, c_int, c_int]),
@@ -37,7 +37,7 @@ MAX_D = 512
 
 
 def kernel_enabled() -> bool:
-    return os.environ.get("CML_GRAM_KERNEL", "1") != "0"
+    return env_enabled("CML_GRAM_KERNEL")
 
 
 def kernel_supported(dtype: torch.dtype, d: int) -> bool:
@@ -46,12 +46,6 @@ def kernel_supported(dtype: torch.dtype, d: int) -> bool:
 
 
 # ---------------------------------------------------------------------------------------------- reference form
-def _widen(v: torch.Tensor) -> torch.Tensor:
-    if v.dtype == torch.float8_e4m3fn:
-        v = v.to(torch.float32)
-    return v.to(torch.float64)
-
-
 def _mirror(g: torch.Tensor) -> torch.Tensor:
     return torch.triu(g) + torch.triu(g, 1).T
 
@@ -71,7 +65,7 @@ def gram_reference(x: torch.Tensor, d: int, z: torch.Tensor, w: Optional[torch.T
     for st in range(0, n, chunk):
         en = min(n, st + chunk)
         a = torch.empty((en - st, m), dtype=torch.float64, device=dev)
-        a[:, :d] = _widen(x[st:en, :d])
+        a[:, :d] = widen(x[st:en, :d])
         a[:, d] = 1.0
         a[:, d + 1] = z[st:en].to(device=dev, dtype=torch.float64)
         if w is None:
@@ -82,11 +76,6 @@ def gram_reference(x: torch.Tensor, d: int, z: torch.Tensor, w: Optional[torch.T
 
 
 # ---------------------------------------------------------------------------------------------------- kernel
-def _ncu(dev) -> int:
-    from ..utils.device import num_cus
-    return num_cus(dev.index if dev.index is not None else torch.cuda.current_device())
-
-
 def _readable_cols(xx: torch.Tensor) -> int:
     """Columns of a row that the kernel's 16-byte loads may touch: the width rounded up to 8 where the row pitch and
     the storage behind the last row cover it, else 0."""
@@ -123,10 +112,10 @@ def gram(x: torch.Tensor, d: int, z: torch.Tensor, w: Optional[torch.Tensor] = N
         xx, wc = buf, int(buf.shape[1])
     zz = z.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
     ww = w.reshape(-1).to(device=dev, dtype=torch.float64).contiguous() if w is not None else None
-    lib, ncu = _native.kernels(), _ncu(dev)
-    slabs = int(lib.cml_gram_mfma_slabs(n, d, ncu))
+    lib, cus = _native.kernels(), ncu(dev)
+    slabs = int(lib.cml_gram_mfma_slabs(n, d, cus))
     part = torch.empty(slabs * int(lib.cml_gram_mfma_part(d)), dtype=torch.float64, device=dev)
     _native.check(lib.cml_gram_mfma(xx.data_ptr(), n, xx.stride(0), wc, d, zz.data_ptr(), _native.ptr(ww),
-                                    part.data_ptr(), slabs, out.data_ptr(), ncu,
+                                    part.data_ptr(), slabs, out.data_ptr(), cus,
                                     torch.cuda.current_stream(dev).cuda_stream), "gram")
     return out

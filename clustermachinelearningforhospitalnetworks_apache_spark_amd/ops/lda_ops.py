@@ -21,13 +21,13 @@ per-workgroup partials in workgroup order. ``CML_LDA_KERNEL=0`` keeps the estima
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 
 from .. import _native
 from .._native import c_int, c_ll, c_vp
+from ._fused import check_matrix, env_enabled, gather_rows, ncu, row_list, widen  # gather_rows: a public name here
 
 _native.register_kernel_sigs({
     "cml_lda_lds": (c_ll, [c_int, c_int]),
@@ -42,7 +42,7 @@ _TILE = 64
 
 
 def kernel_enabled() -> bool:
-    return os.environ.get("CML_LDA_KERNEL", "1") != "0"
+    return env_enabled("CML_LDA_KERNEL")
 
 
 def lds_bytes(dp: int, k: int) -> int:
@@ -67,27 +67,12 @@ def kernel_supported(dtype: torch.dtype, dp: int, k: int) -> bool:
 
 
 # ---------------------------------------------------------------------------------------------- reference form
-def _widen(v: torch.Tensor) -> torch.Tensor:
-    if v.dtype == torch.float8_e4m3fn:
-        v = v.to(torch.float32)
-    return v.to(torch.float64)
-
-
-def gather_rows(x: torch.Tensor, idx: Optional[torch.Tensor], d: int) -> torch.Tensor:
-    """Rows ``idx`` (None: all) of a column of any dtype, widened to f64 (e4m3 rows are gathered as bytes)."""
-    if idx is None:
-        return _widen(x[:, :d])
-    if x.dtype == torch.float8_e4m3fn:
-        return _widen(x.view(torch.uint8)[idx].view(torch.float8_e4m3fn)[:, :d])
-    return _widen(x[idx][:, :d])
-
-
 def row_sums(x: torch.Tensor, d: int, chunk: int = 1 << 16) -> torch.Tensor:
     """f64 ``[n]`` row sums over the first ``d`` columns, one widened chunk at a time."""
     n = int(x.shape[0])
     out = torch.empty(n, dtype=torch.float64, device=x.device)
     for st in range(0, n, chunk):
-        out[st:st + chunk] = _widen(x[st:st + chunk, :d]).sum(1)
+        out[st:st + chunk] = widen(x[st:st + chunk, :d]).sum(1)
     return out
 
 
@@ -112,7 +97,7 @@ def estep_reference(x: torch.Tensor, rows: Optional[torch.Tensor], d: int, e_bet
     margin = float("inf")
     for st in range(0, B, chunk):
         if rows is None:
-            v = _widen(x[st:st + chunk, :d])
+            v = widen(x[st:st + chunk, :d])
         else:
             v = gather_rows(x, rows[st:st + chunk].to(dev), d)
         g, ss, _, _, sw, mg = e_step_counted(v, e_beta, alpha, gamma0[st:st + chunk], with_margin=with_margin)
@@ -127,25 +112,17 @@ def estep_reference(x: torch.Tensor, rows: Optional[torch.Tensor], d: int, e_bet
 
 
 # ---------------------------------------------------------------------------------------------------- kernel
-def _ncu(dev) -> int:
-    from ..utils.device import num_cus
-    return num_cus(dev.index if dev.index is not None else torch.cuda.current_device())
-
-
 def _launch(xd, rows, d, e_beta, alpha, gamma0, fit: bool, what: str):
     if not torch.is_tensor(xd) or xd.dim() != 2:
         raise ValueError(f"{what}: rows must be a 2-d tensor")
     k = int(e_beta.shape[0])
     dp = int(xd.shape[1])
-    if (not xd.is_cuda or not xd.is_contiguous() or not kernel_supported(xd.dtype, dp, k) or not 1 <= d <= dp
-            or e_beta.shape[1] != d or alpha.shape != (k,)):
-        raise ValueError(f"{what}: rows must be a contiguous bf16 device matrix of padded width 16..512, with "
-                         "e_beta [k, d], alpha [k] and k inside the kernel's limits")
+    check_matrix(xd, d, lambda dtype, dp: (kernel_supported(dtype, dp, k) and e_beta.shape[1] == d
+                                           and alpha.shape == (k,)), what,
+                 "16..512, with e_beta [k, d], alpha [k] and k inside the kernel's limits")
     n, dev = int(xd.shape[0]), xd.device
     if rows is not None:
-        if rows.dtype != torch.int64 or rows.dim() != 1:
-            raise ValueError(f"{what}: the row list must be an int64 vector")
-        rows = rows.to(dev).contiguous()
+        rows = row_list(rows, dev, what)
     B = n if rows is None else int(rows.shape[0])
     if gamma0.shape != (B, k):
         raise ValueError(f"{what}: gamma0 must be [B, k]")
@@ -159,12 +136,12 @@ def _launch(xd, rows, d, e_beta, alpha, gamma0, fit: bool, what: str):
         al = torch.zeros(kp, dtype=torch.float64, device=dev)
         al[:k] = alpha.to(device=dev, dtype=torch.float64)
         g0 = gamma0.to(device=dev, dtype=torch.float64).contiguous()
-        lib, ncu = _native.kernels(), _ncu(dev)
-        grid = int(lib.cml_lda_grid(B, dp, k, ncu))
+        lib, cus = _native.kernels(), ncu(dev)
+        grid = int(lib.cml_lda_grid(B, dp, k, cus))
         part = torch.empty(grid * (kp * dp + kp), dtype=torch.float64, device=dev) if fit else None
         _native.check(lib.cml_lda_estep(xd.data_ptr(), n, dp, d, k, _native.ptr(rows), B, tab.data_ptr(),
                                         al.data_ptr(), g0.data_ptr(), gamma.data_ptr(), sweeps.data_ptr(),
-                                        _native.ptr(part), grid, _native.ptr(out), 1 if fit else 0, ncu,
+                                        _native.ptr(part), grid, _native.ptr(out), 1 if fit else 0, cus,
                                         torch.cuda.current_stream(dev).cuda_stream), what)
     return gamma, sweeps, out
 

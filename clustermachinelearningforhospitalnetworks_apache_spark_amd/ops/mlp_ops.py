@@ -22,13 +22,13 @@ reference form.
 """
 from __future__ import annotations
 
-import os
 from typing import List, Sequence
 
 import torch
 
 from .. import _native
 from .._native import c_int, c_ll, c_vp
+from ._fused import check_matrix, env_enabled, ncu, widen
 
 _native.register_kernel_sigs({
     "cml_mlp_lds": (c_ll, [c_int, c_int, c_int]),
@@ -42,7 +42,7 @@ _TILE = 64
 
 
 def kernel_enabled() -> bool:
-    return os.environ.get("CML_MLP_KERNEL", "1") != "0"
+    return env_enabled("CML_MLP_KERNEL")
 
 
 def size(layers: Sequence[int]) -> int:
@@ -81,12 +81,6 @@ def kernel_supported(dtype: torch.dtype, dp: int, layers: Sequence[int]) -> bool
 
 
 # ---------------------------------------------------------------------------------------------- reference form
-def _widen(v: torch.Tensor) -> torch.Tensor:
-    if v.dtype == torch.float8_e4m3fn:
-        v = v.to(torch.float32)
-    return v.to(torch.float64)
-
-
 def _unpack(p: torch.Tensor, layers: Sequence[int]):
     out, off = [], 0
     for a, b in zip(layers[:-1], layers[1:]):
@@ -129,7 +123,7 @@ def loss_grad_reference(x: torch.Tensor, d: int, y: torch.Tensor, layers: Sequen
     gb = [torch.zeros(b.shape, dtype=torch.float64, device=dev) for _, b in params]
     loss = torch.zeros((), dtype=torch.float64, device=dev)
     for st in range(0, n, chunk):
-        acts = _forward_chunk(_widen(x[st:st + chunk, :d]), params)
+        acts = _forward_chunk(widen(x[st:st + chunk, :d]), params)
         yc = y[st:st + chunk].to(device=dev, dtype=torch.int64)[:, None]
         z = acts[-1]
         m = z.max(1, keepdim=True).values
@@ -153,16 +147,11 @@ def forward_reference(x: torch.Tensor, d: int, layers: Sequence[int], p, chunk: 
     n = int(x.shape[0])
     out = torch.empty(n, layers[-1], dtype=torch.float64, device=x.device)
     for st in range(0, n, chunk):
-        out[st:st + chunk] = _forward_chunk(_widen(x[st:st + chunk, :d]), params)[-1]
+        out[st:st + chunk] = _forward_chunk(widen(x[st:st + chunk, :d]), params)[-1]
     return out
 
 
 # ---------------------------------------------------------------------------------------------------- kernel
-def _ncu(dev) -> int:
-    from ..utils.device import num_cus
-    return num_cus(dev.index if dev.index is not None else torch.cuda.current_device())
-
-
 def _pack(p: torch.Tensor, layers: List[int], dp: int) -> torch.Tensor:
     """The kernel's parameter image: W_1 ``[hp, dp]``, W_l ``[hp out, hp in]`` for the upper layers, then the
     biases ``[L, hp]``, zero padded."""
@@ -185,10 +174,8 @@ def _launch(xd, d, y32, layers, p, fit: bool, what: str):
         raise ValueError(f"{what}: rows must be a 2-d tensor")
     dp = int(xd.shape[1])
     layers = [int(v) for v in layers]
-    if (not xd.is_cuda or not xd.is_contiguous() or not kernel_supported(xd.dtype, dp, layers) or not 1 <= d <= dp
-            or layers[0] != d):
-        raise ValueError(f"{what}: rows must be a contiguous bf16 device matrix of padded width 16..512 and layers "
-                         "[d, ..] a topology inside the kernel's limits")
+    check_matrix(xd, d, lambda dtype, dp: kernel_supported(dtype, dp, layers) and layers[0] == d, what,
+                 "16..512 and layers [d, ..] a topology inside the kernel's limits")
     n, dev = int(xd.shape[0]), xd.device
     p = torch.as_tensor(p)
     if p.dim() != 1 or p.numel() != size(layers):
@@ -204,13 +191,13 @@ def _launch(xd, d, y32, layers, p, fit: bool, what: str):
         nl, hmax = len(layers) - 1, max(layers[1:])
         hp = 16 if hmax <= 16 else 32
         wp = _pack(p.to(device=dev, dtype=torch.float64), layers, dp)
-        lib, ncu = _native.kernels(), _ncu(dev)
-        grid = int(lib.cml_mlp_grid(n, dp, hmax, nl, ncu))
+        lib, cus = _native.kernels(), ncu(dev)
+        grid = int(lib.cml_mlp_grid(n, dp, hmax, nl, cus))
         part = torch.empty(grid * (hp * dp + (nl - 1) * hp * hp + nl * hp + 1), dtype=torch.float64,
                            device=dev) if fit else None
         s = layers[1:] + [0] * (4 - len(layers))
         _native.check(lib.cml_mlp_pass(xd.data_ptr(), n, dp, d, nl, s[0], s[1], s[2], _native.ptr(y32 if fit else None),
-                                       wp.data_ptr(), _native.ptr(part), grid, out.data_ptr(), 1 if fit else 0, ncu,
+                                       wp.data_ptr(), _native.ptr(part), grid, out.data_ptr(), 1 if fit else 0, cus,
                                        torch.cuda.current_stream(dev).cuda_stream), what)
     return out
 
