@@ -6,7 +6,7 @@
 // forest at once ("ensemble packing"), splits chosen on the host from the all-reduced
 // histograms, rows routed to children on the device.
 //
-// K17 tree_binize  value -> bin: #thresholds < value (binary search, thresholds in LDS);
+// K17 tree_binize  value -> bin: #thresholds < value, NaN above all (binary search, thresholds in LDS);
 //                  uint8 codes up to 256 bins, uint16 above
 // K18 tree_hist    hist[t][node][f][bin][s] += w_t(row)·stat_s(row) for rows whose node
 //                  at this level is `node`; LDS-privatised per workgroup (one tree ×
@@ -23,6 +23,9 @@ namespace {
 // Bin codes are uint8 while nbins <= 256 (Spark's default maxBins = 32) and uint16 above it, so
 // maxBins > 256 never wraps. Thresholds sit in LDS when d * max_splits doubles fit 64 KiB; wider
 // tables (d = 512 features, large maxBins) are read from global memory (L2-resident, read-only).
+// A NaN value compares above every threshold and gets bin nsplit[f], like the host form
+// (searchsorted orders NaN last) and like K21 and the host predictor, where `x <= thr` is false for
+// NaN and the row goes right: training and prediction route a NaN cell the same way.
 template <typename BinT, bool kLds>
 __global__ void tree_binize_kernel(const double* __restrict__ X, long long n, long long ld, int d,
                                    const double* __restrict__ thr, int max_splits, const int* __restrict__ nsplit,
@@ -40,10 +43,10 @@ __global__ void tree_binize_kernel(const double* __restrict__ X, long long n, lo
     const int f = (int)(i - r * d);
     const double v = X[r * ld + f];
     const double* t = tab + (long long)f * max_splits;
-    int lo = 0, hi = nsplit[f];  // first index with t[idx] >= v
+    int lo = 0, hi = nsplit[f];  // first index with t[idx] >= v; nsplit[f] when v is NaN
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (t[mid] < v) lo = mid + 1; else hi = mid;
+      if (!(t[mid] >= v)) lo = mid + 1; else hi = mid;
     }
     bins[r * d + f] = (BinT)lo;
   }

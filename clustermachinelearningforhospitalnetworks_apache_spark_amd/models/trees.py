@@ -228,6 +228,10 @@ class ForestEngine:
         return [continuous_splits(allv[:, j], p.max_bins - 1) for j in range(self.d)]
 
     def binize(self, splits: List[np.ndarray]) -> torch.Tensor:
+        """Bin codes [n, d]: per cell the number of the feature's thresholds below the value (so a value
+        equal to a threshold stays left of it). NaN orders above every threshold and gets the last bin,
+        ``len(splits[f])``, on both paths (K17 and searchsorted): a NaN cell goes right in training as
+        it does in prediction, where ``x <= threshold`` is false."""
         ms = max(1, max((len(s) for s in splits), default=1))
         thr = np.full((self.d, ms), np.inf)
         ns = np.zeros(self.d, dtype=np.int32)
@@ -460,12 +464,13 @@ class ForestEngine:
         -1: none). Spark's binsToBestSplit takes the first maximum in (feature, bin) order; exact ties (two
         features separating the same rows of a small node) are common and rounding breaks them arbitrarily,
         so both paths take the first (feature, bin) within TIE_REL·|G| of the maximum G. GPU: one workgroup
-        per node on the fixed-point histogram; CPU: the same rule vectorised in numpy."""
+        per node on the fixed-point histogram; CPU, and class counts wider than the kernel's 16 statistics
+        (like predict_forest and forest_vote): the same rule vectorised in numpy on the host."""
         T, S, d, nb = self.p.num_trees, self.S, self.d, self.nbins
         p = self.p
         kind_id = {"variance": 0, "gini": 1, "entropy": 2}[self.kind]
         nsplit = np.array([len(sp) for sp in self.splits], dtype=np.int32)
-        if self.gpu:
+        if self.gpu and S <= K19_MAX_STATS:
             out = torch.empty((T * nodes, 3 + 3 * S), dtype=torch.float64, device=self.dev)
             sc = torch.as_tensor(self.scales, dtype=torch.float64, device=self.dev)
             mk = torch.as_tensor(masks.reshape(-1), device=self.dev)
@@ -522,6 +527,7 @@ class ForestEngine:
 
 
 TIE_REL = 1e-12  # kTreeTieRel in trees.hip
+K19_MAX_STATS = 16  # kTreeSMax in trees.hip
 
 
 def _impurity_vec(st: np.ndarray, kind: str) -> np.ndarray:
