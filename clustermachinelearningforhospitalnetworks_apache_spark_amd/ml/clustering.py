@@ -113,7 +113,7 @@ class KMeans(Estimator):
         else:
             with trace("kmeans.init"):
                 init = eng.init_kmeans_parallel(seed, self.getInitSteps(), as_device=True)
-            k_eff = getattr(eng, "k_effective", k)
+            k_eff = eng.k_effective
             if k_eff < k:
                 init = init[:k_eff]
                 eng = LloydEngine(x, d, k_eff, comm, row_ids=df._row_ids, spherical=spherical, prune=prune,

@@ -21,7 +21,7 @@ out, exact in f64 for bf16/fp8 rows), falling back to the full accumulate on the
 whenever more than 1/4 of the rows changed (CML_KMEANS_DELTA_CAP). Every step still assigns every row against every centre.
 
 Pruned steps (``prune=True`` / ``CML_KMEANS_PRUNE=1``, opt-in): the exact bound-pruned form of the
-same iteration (``_step_prune``). Spark's own findClosest skips centres the triangle inequality rules
+same iteration (``_step_prune_dev``; ``kmeans_prune_host._step_prune``). Spark's own findClosest skips centres the triangle inequality rules
 out (mllib/clustering/DistanceMeasure.scala); here a per-row upper bound on the distance to the
 assigned centre is carried across iterations (Hamerly), so rows whose bound proves the label are not
 read at all and only the others are re-assigned against every centre. Labels, sums and centres are
@@ -37,6 +37,14 @@ beyond that the result is still deterministic for a fixed partition.
 
 CPU tensors run the same algorithm with torch float64 ops (``local[n]`` mode and
 the numerical oracle).
+
+Where the parts live: this module holds ``LloydEngine`` — the constructor, the step dispatch, the MFMA steps
+(full, weighted, screened exact, device pruned with its launch replay), the graph wrapper, the CPU step and the
+cost readers. ``kmeans_route.py`` decides the path from the constructor's arguments (``resolve_route``, a pure
+function; the plan-dependent second stage is the block at the top of ``_alloc_gpu``); ``kmeans_init.py`` is
+k-means|| and the random init; ``kmeans_prune_host.py`` the host-synchronised pruned step (host rows, device rows
+without a K9r plan); ``kmeans_layout.py`` the row layouts and per-tensor caches. The three are plain functions
+over the engine; their names are re-exported here.
 """
 from __future__ import annotations
 
@@ -52,151 +60,13 @@ from .. import _native
 from ..ops import kmeans_ops as K
 from ..ops.group_ops import group_reduce
 from ..parallel.comm import Communicator, local_comm
-from ..utils import rng
 from ..utils.device import padded_dim, round_up
 from ..utils.fault import maybe_fail
 from ..utils.trace import trace
-
-
-def padded_dim_fp8(d: int) -> int:
-    """fp8 rows: >= 256 bytes, power of two (16-B loads covering two MFMA k-steps, sort-regime lanes)."""
-    return max(256, 1 << max(0, (d - 1).bit_length()))
-
-
-def to_device_matrix(x: torch.Tensor, d: Optional[int] = None) -> torch.Tensor:
-    """Zero-padded GPU copy of a feature matrix in the kernels' layout: bf16 [n, padded_dim(d)], or
-    OCP e4m3fn [n, padded_dim_fp8(d)] when the features already are fp8 (SURVEY config 5)."""
-    d = x.shape[1] if d is None else d
-    if x.dtype == torch.float8_e4m3fn:
-        dp = padded_dim_fp8(d)
-        if x.shape[1] == dp and x.is_contiguous():
-            return x
-        out = torch.zeros((x.shape[0], dp), dtype=torch.uint8, device=x.device)
-        out[:, :d] = x[:, :d].view(torch.uint8)
-        return out.view(torch.float8_e4m3fn)
-    dp = padded_dim(d)
-    if x.dtype == torch.bfloat16 and x.shape[1] == dp and x.is_contiguous():
-        return x
-    out = torch.zeros((x.shape[0], dp), dtype=torch.bfloat16, device=x.device)
-    step = 1 << 22
-    for s in range(0, x.shape[0], step):
-        out[s:s + step, :d] = x[s:s + step, :d].to(torch.bfloat16)
-    return out
-
-
-def host_layout(x: torch.Tensor, d: Optional[int] = None) -> torch.Tensor:
-    """The pinned host copy of an out-of-core feature matrix in the kernels' layout (bf16
-    [n, padded_dim(d)], or e4m3fn [n, padded_dim_fp8(d)] for fp8 rows), written straight into page-locked
-    memory chunk by chunk (no unpinned intermediate) and cached on ``x`` while it is unmodified, so the
-    fits and transforms of one column share one copy — and, through it, the cached row norms and stream
-    buffers (every transform used to make a new bf16 copy plus a pinned copy of it). A matrix
-    already in that layout and pinned is used as is."""
-    from ..utils.hoststream import pinned_rows
-    d = x.shape[1] if d is None else d
-    fp8 = x.dtype == torch.float8_e4m3fn
-    dp = padded_dim_fp8(d) if fp8 else padded_dim(d)
-    want = torch.float8_e4m3fn if fp8 else torch.bfloat16
-    layout = x.dtype == want and x.shape[1] == dp and x.is_contiguous()
-    if layout and (x.is_pinned() or not torch.cuda.is_available()):
-        return x
-    ent = getattr(x, "_cml_hostlayout", None)
-    if ent is not None and ent[0] == x._version and ent[1] == d:
-        return ent[2]
-    pin = torch.cuda.is_available()
-    n = x.shape[0]
-    if layout:
-        out = pinned_rows(x)
-    elif fp8:
-        out = torch.zeros((n, dp), dtype=torch.uint8, pin_memory=pin)
-        out[:, :d] = x[:, :d].view(torch.uint8)
-        out = out.view(torch.float8_e4m3fn)
-    else:
-        out = torch.zeros((n, dp), dtype=torch.bfloat16, pin_memory=pin)
-        step = 1 << 20
-        for s in range(0, n, step):
-            out[s:s + step, :d] = x[s:s + step, :d].to(torch.bfloat16)
-    try:
-        x._cml_hostlayout = (x._version, d, out)
-    except (AttributeError, RuntimeError):
-        pass
-    return out
-
-
-def unit_rows(x: torch.Tensor, d: Optional[int] = None, exact: Optional[bool] = None) -> torch.Tensor:
-    """Rows scaled to unit length (cosine KMeans). bf16 on the GPU's MFMA path (computed in f32; fp8
-    inputs widen to bf16: unit components need more than e4m3's 3 mantissa bits), f64 on the CPU and
-    on the GPU's source-precision path (``exact``, default: f32/f64 input). Spark rejects zero-length
-    vectors for the cosine measure, and so does this."""
-    d = x.shape[1] if d is None else d
-    if exact is None:
-        exact = (not x.is_cuda) or x.dtype in (torch.float32, torch.float64)
-    out_dtype = torch.float64 if exact else torch.bfloat16
-    work = torch.float64 if exact else torch.float32
-    out = torch.empty((x.shape[0], d), dtype=out_dtype, device=x.device)
-    step = 1 << 22
-    for s in range(0, x.shape[0], step):
-        v = x[s:s + step, :d].to(work)
-        nrm = v.norm(dim=1, keepdim=True)
-        if bool((nrm == 0).any()):
-            raise ValueError("Cosine distance is not defined for zero-length vectors.")
-        out[s:s + step] = (v / nrm).to(out_dtype)
-    return out
-
-
-def dd_sums_exact(x: torch.Tensor, d: int, comm: Communicator) -> bool:
-    """Whether double-double sums of the f64 rows are exact in any order (so incremental, chunked and
-    rank-folded sums agree bit for bit): a value is a multiple of 2^(e_min - 52) and a total of n of them
-    stays below 2^(e_max + 1 + log2 n), which a double-double (2 x 53 bits) holds while
-    e_max - e_min + 53 + log2(n) <= 104 (2 bits of margin). One pass over the rows (cached on the tensor
-    while it is unmodified); the span and the row count are agreed over every rank (a collective)."""
-    ent = getattr(x, "_cml_f64span", None)
-    if ent is not None and ent[0] == x._version and ent[1] == d:
-        lo, hi = ent[2], ent[3]
-    else:
-        lo, hi = math.inf, -math.inf
-        step = max(1, (1 << 24) // max(d, 1))
-        for r0 in range(0, int(x.shape[0]), step):
-            a = x[r0:r0 + step, :d].abs()
-            mx = float(a.max()) if a.numel() else 0.0
-            if mx > 0:
-                mn = float(torch.where(a > 0, a, torch.full_like(a, math.inf)).min())
-                hi = max(hi, math.frexp(mx)[1])
-                lo = min(lo, math.frexp(mn)[1])
-        try:
-            x._cml_f64span = (x._version, d, lo, hi)
-        except (AttributeError, RuntimeError):
-            pass
-    v = torch.tensor([-lo if lo != math.inf else -1e9, hi if hi != -math.inf else -1e9, float(x.shape[0])],
-                     dtype=torch.float64, device=comm.device)
-    if comm.is_distributed:
-        comm.allreduce_(v[:2], op="max")
-        comm.allreduce_(v[2:], op="sum")
-    lo_g, hi_g, n_g = -float(v[0]), float(v[1]), float(v[2])
-    if hi_g < -1e8:  # every value is zero
-        return True
-    return (hi_g - lo_g) + 53 + math.ceil(math.log2(n_g + 1)) <= 104
-
-
-def cached_row_sqnorm(x: torch.Tensor, n: int, dp: int) -> torch.Tensor:
-    """||x_i||² of the device matrix's rows, kept on the tensor itself while it is unmodified.
-
-    Spark caches point norms with the vectors (reference KMeans uses VectorWithNorm); here the cache
-    rides on the feature tensor, so a fit followed by ``KMeansModel.transform``/``computeCost`` on the
-    same features reads the matrix once for its norms instead of once per call. The entry is keyed by
-    the tensor's version counter: any in-place write invalidates it."""
-    ent = getattr(x, "_cml_xnorm", None)
-    if ent is not None and ent[0] == x._version and ent[1] == (n, dp):
-        return ent[2]
-    xn = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-    xn64 = torch.empty(max(n, 1), dtype=torch.float64, device=x.device)
-    er = torch.tensor([2 ** 31 - 1, -1], dtype=torch.int32, device=x.device)
-    if n:
-        K.row_pass(x, n, dp, xn, erange=er, xn64=xn64)
-    try:
-        x._cml_xnorm = (x._version, (n, dp), xn, er, xn64)
-    except (AttributeError, RuntimeError):
-        pass
-    return xn
+from . import kmeans_init, kmeans_prune_host
+from .kmeans_layout import (cached_row_norms, cached_row_sqnorm, dd_sums_exact, host_layout,  # noqa: F401
+                            padded_dim_fp8, to_device_matrix, unit_rows)
+from .kmeans_route import resolve_route
 
 
 class LloydEngine:
@@ -215,104 +85,36 @@ class LloydEngine:
         # norms, labels, k-means|| costs — lives on the device)
         self._hs = None
         streamed = device is not None and torch.device(device).type == "cuda" and not x.is_cuda
+        screen_ok = (x.is_cuda and x.dtype in (torch.float32, torch.float64) and not streamed and weights is None
+                     and not spherical and self.screen_applies(d, k))
+        # every decision taken before the rows are prepared (kmeans_route.py; dd_sums_exact is a collective)
+        rt = resolve_route(on_device=x.is_cuda, dtype=x.dtype, streamed=streamed, weighted=weights is not None,
+                           spherical=bool(spherical), precision=precision, prune=prune, incremental=incremental,
+                           use_graph=use_graph, row_chunks=row_chunks, accum_mode=accum_mode,
+                           refresh_interval=refresh_interval, screen_ok=screen_ok,
+                           dd_exact=lambda: dd_sums_exact(x, d, self.comm), env=os.environ)
+        self.precision, self.prune, self.gpu = rt.precision, rt.prune, rt.gpu
+        self._wfast, self._screen = rt.wfast, rt.screen
+        self._accum_mode, self._incremental = rt.accum_mode, rt.incremental
+        self.use_graph, self.refresh_interval, row_chunks = rt.use_graph, rt.refresh_interval, rt.row_chunks
         if streamed:
-            if weights is not None or spherical:
-                raise ValueError("streamed (out-of-core) KMeans supports unweighted euclidean fits")
             # the pinned bf16/fp8 padded copy, made once per column and reused by every later fit and
             # transform of it (with its cached norms and its stream buffers)
             x = host_layout(x, d)
-            precision, prune, incremental, use_graph = "bf16", False, False, False
-        # full re-accumulation of the incremental sums every refresh_interval steps (0 = never: the sum
-        # grid of _sum_grid already keeps incremental == full bit for bit; conf
-        # cml.ml.kmeans.refreshInterval / env CML_KMEANS_REFRESH turn on the belt-and-braces refresh)
-        if refresh_interval is None:
-            refresh_interval = int(os.environ.get("CML_KMEANS_REFRESH", "0") or 0)
-        self.refresh_interval = max(0, int(refresh_interval))
-        # weights (Spark's weightCol, KMeans.scala runAlgorithm): centre = Σ w·x / Σ w, cost = Σ w·d²,
-        # k-means|| candidates weighted by the summed weight of their rows. Weighted fits run the
-        # source-precision path (f64 rows, deterministic f64 sums of [w·x | w]) unless precision "bf16" is
-        # asked for (argument, conf cml.ml.kmeans.precision, env CML_KMEANS_PRECISION): device rows then
-        # stay bf16 / e4m3 on the MFMA path (_step_weighted: K9 / K9r assign, the counting sort, the
-        # double-double weighted sums of K10w — the same correctly rounded Σ fl64(w·x) the source-precision
-        # path forms, with no f64 copy of X). "auto" keeps the source-precision routing; host rows with
-        # "bf16" take the host path, as an unweighted "bf16" request on host rows does.
-        self._wfast = False
-        if weights is not None:
-            req = str(precision or os.environ.get("CML_KMEANS_PRECISION") or "auto").lower()
-            if req == "bf16" and x.is_cuda:
-                self._wfast = True
-                precision, prune, incremental, use_graph = "bf16", False, False, False
-                row_chunks, accum_mode = 1, "sort"
-            else:
-                precision, prune = "exact", False
-                if x.is_cuda and x.dtype not in (torch.float32, torch.float64):
-                    x = x.to(torch.float32)
-        # precision (cml.ml.kmeans.precision): "bf16" = the MFMA path (bf16 rows in the distance GEMM,
-        # exact f64 sums of those rows); "exact" = the f64 reference algorithm on the rows as given
-        # (kmeans_exact.hip on the GPU); "auto" = exact for f32/f64 device rows — the reference's f64
-        # feature vectors (ref.py:134-136) are not silently rounded to 8 mantissa bits — and the MFMA
-        # path for bf16 / fp8 rows; "screen" = the exact algorithm's results bit for bit, with the
-        # assignments screened on MFMA (_screen_labels: a bf16 K9r pass with top-2 bounds, a certificate
-        # covering the bf16 rounding of rows and centres, an f64 re-assignment of the uncertified rows) —
-        # what "auto" picks for wide f32/f64 device rows where K9r applies (CML_KMEANS_SCREEN=0: exact).
-        precision = (precision or os.environ.get("CML_KMEANS_PRECISION") or "auto").lower()
-        if precision not in ("auto", "bf16", "exact", "screen"):
-            raise ValueError(f"KMeans precision must be 'auto', 'bf16', 'exact' or 'screen', got {precision!r}")
-        src_prec = x.is_cuda and x.dtype in (torch.float32, torch.float64)
-        screen_ok = (src_prec and not streamed and weights is None and not spherical and
-                     self.screen_applies(d, k))
-        if precision == "auto":
-            precision = "exact" if (not x.is_cuda or x.dtype in (torch.float32, torch.float64)) else "bf16"
-            if precision == "exact" and screen_ok and os.environ.get("CML_KMEANS_SCREEN", "1") != "0":
-                # the screen's incremental double-double sums equal the exact path's only while every
-                # coordinate sum fits 106 bits: f32 rows always; f64 rows when their exponent span allows
-                #  — otherwise the plain exact kernels
-                if x.dtype != torch.float64 or dd_sums_exact(x, d, self.comm):
-                    precision = "screen"
-        if streamed:
-            precision = "bf16"
-        if precision in ("exact", "screen") and x.is_cuda and x.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"precision {precision!r} needs f32/f64 rows, got {x.dtype}")
-        if precision == "screen" and not screen_ok:
-            precision = "exact"  # (weights, cosine, or no K9r plan at this width: the plain exact kernels)
-        self.precision = precision
-        self._screen = precision == "screen"
-        exact_dev = x.is_cuda and precision in ("exact", "screen")
-        if exact_dev:
-            prune = False  # the reference algorithm (the torch bounds form would need host syncs anyway)
-        if prune is None:  # default on GPU rows: exact pruned steps (CML_KMEANS_PRUNE=0 turns them off)
-            env = os.environ.get("CML_KMEANS_PRUNE")
-            prune = (env != "0") if env is not None else x.is_cuda
-        self.prune = bool(prune)
-        self.track_prune = False  # record (full?, re-assigned rows) of every pruned step (host reads)
-        self._pdev = False  # the device pruned step (_step_prune_dev) is in use, decided in _alloc_gpu
-        if self.prune:  # one row chunk; the device form keeps incremental sums, the torch form its own
-            row_chunks = 1
+        if rt.to_f32:
+            x = x.to(torch.float32)
         # spherical = Spark's distanceMeasure="cosine": rows are scaled to unit length once, centres
         # are renormalised after every update (CosineDistanceMeasure.centroid), and on unit vectors
         # ||x - c||² = 2·(1 - cos), so the euclidean K9/K10 path computes the cosine assignment;
         # costs and the convergence test are converted back (cost / 2, shift² <= 2·tol).
         self.spherical = bool(spherical)
         if self.spherical:
-            x = unit_rows(x, d, exact=(precision == "exact"))
-        self._accum_mode = accum_mode
-        self._incremental = True if incremental is None else bool(incremental)
-        # One Lloyd step = ~8-15 kernel launches; with use_graph it is replayed as a captured HIP graph
-        # (single rank: one graph; multi-rank: the device pruned step as two graphs around its
-        # all-reduce, the RCCL call eager between the replays; the chunked full step stays eager).
-        # Measured on MI355X (profiles/r3/graph_ab/): the pruned step has no host synchronisation, so eager
-        # launches run ahead of the GPU and a 20-step fit is as fast eagerly (100.9 vs 102.6 ms at 100M
-        # rows, 19.6 vs 20.9 ms at the 8-GPU shard of 12.5M) — the capture costs more than the replays
-        # save. Default eager; CML_KMEANS_GRAPH=1 (or use_graph=True) captures.
-        if use_graph is None:
-            use_graph = os.environ.get("CML_KMEANS_GRAPH") == "1"
-        self.use_graph = bool(use_graph)
+            x = unit_rows(x, d, exact=(rt.precision == "exact"))
+        self.track_prune = False  # record (full?, re-assigned rows) of every pruned step (host reads)
+        self._pdev = False  # the device pruned step (_step_prune_dev) is in use, decided in _alloc_gpu
         self._graph = None
         self.k = int(k)
         self.d = int(d)
-        # the MFMA kernels run only on the bf16 path; the exact path runs the reference algorithm (the
-        # torch f64 ops, with the f64 HIP kernels for assignment and sums) on the rows' device
-        self.gpu = (x.is_cuda or streamed) and precision == "bf16"
         self.n = int(x.shape[0])
         self.device = torch.device(device) if streamed else x.device
         self._scr = None  # screen state (precision "screen"), see _screen_state
@@ -377,7 +179,7 @@ class LloydEngine:
         self._shift2 = None
         self._conv_lim = None  # squared-move limit of a tol > 0 fit's device convergence latch (_fit_lagged)
         self.delta = None  # incremental-sums state (GPU sort regime), see _alloc_gpu
-        self._pst = None  # pruned-step state, see _step_prune
+        self._pst = None  # pruned-step state: _pdev_alloc, or kmeans_prune_host._prune_init
         # sum grid of the device sort-regime accumulates (_sum_grid): qscale 0 / unit 1 = plain f64 sums
         self._qscale, self._unit, self._grid_done = 0.0, 1.0, False
         self.sum_grid = None  # the grid step when the rows are summed on a grid
@@ -392,8 +194,9 @@ class LloydEngine:
         self._graph_warm = False
         self._scr_scratch = None
         self._shift_pair = None
-        self._iscr = None  # scratch of the k-means|| candidate passes (_init_scratch)
-        self._rr_max = None  # _rr_max_chunk
+        self._iscr = None  # scratch of the k-means|| candidate passes (kmeans_init._init_scratch)
+        self._xn64 = None  # ||x||² of host rows in f64 (kmeans_prune_host._prune_init)
+        self.k_effective = self.k  # distinct centres the k-means|| init found (kmeans_init._init_finish)
         self._wst = None  # buffers of the weighted MFMA step (_step_weighted)
         self._init_prune_history = []  # (rows, per-row path, K9r pass) of the pruned k-means|| rounds (track_prune)
         if self.gpu:
@@ -415,23 +218,33 @@ class LloydEngine:
         fp8 = K.is_fp8(self.x)
         self.aplan = K.plan_assign(max(maxn, 1), dp, k, dev.index or 0, fp8=fp8)
         self.cplan = K.plan_accum(max(maxn, 1), dp, k, dev.index or 0, force=self._accum_mode, fp8=fp8)
+        # the second stage of the route (kmeans_route.py), which depends on the plans:
+        # - the device pruned step needs the K9r assign (every centre in one launch) and the sort-regime sums;
+        #   pruned steps without them take the torch form (kmeans_prune_host.py: host-synchronised, never
+        #   captured, its own sums and a per-row distance scratch)
+        # - incremental sums need the sort regime with the centres in one LDS chunk (labels are final after one
+        #   launch); the device pruned step allocates its own, larger change lists in _pdev_alloc
+        # - distance scratch otherwise only when the centres need several LDS chunks (running min through HBM)
+        one_launch = self.aplan.kc == self.aplan.kp
+        self._pdev = self.prune and self.aplan.rr_ct > 0 and one_launch and self.cplan.mode == "sort"
+        torch_prune = self.prune and not self._pdev
+        if torch_prune:
+            self.use_graph = False
+        want_delta = self._incremental and self.cplan.mode == "sort" and one_launch and not self.prune
+        want_best = not one_launch or torch_prune
         self.labels = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        # distance scratch only when the centres need several LDS chunks (running min through HBM)
-        pdev_ok = self.aplan.rr_ct > 0 and self.aplan.kc == self.aplan.kp and self.cplan.mode == "sort"
-        self.best = (torch.zeros(max(n, 1), dtype=torch.float32, device=dev)
-                     if (self.aplan.kc < self.aplan.kp or (self.prune and not pdev_ok)) else None)
+        self.best = torch.zeros(max(n, 1), dtype=torch.float32, device=dev) if want_best else None
         # ||x||² are constant over the fit, like Spark's cached point norms: reused from the feature
         # tensor's cache, else computed lazily (_ensure_norms) — k-means|| init fuses them into its
         # first pass over X
-        ent = getattr(self.x, "_cml_xnorm", None)
-        self._erange = None  # bf16 exponent range of X (exactness of the f64 sums), from the row pass
-        self._xnorm64 = None  # ||x||² summed in f64 (training cost), from the same pass
-        if ent is not None and ent[0] == self.x._version and ent[1] == (n, dp):
-            self._xnorm, self._norms_ready = ent[2], True
-            self._erange = ent[3] if len(ent) > 3 else None
-            self._xnorm64 = ent[4] if len(ent) > 4 else None
+        # (_erange: bf16 exponent range of X — exactness of the f64 sums; _xnorm64: ||x||² summed in f64 — the
+        # training cost; both from the row pass)
+        ent = cached_row_norms(self.x, n, dp)
+        if ent is not None:
+            (self._xnorm, self._erange, self._xnorm64), self._norms_ready = ent, True
         else:
             self._xnorm, self._norms_ready = torch.empty(max(n, 1), dtype=torch.float32, device=dev), False
+            self._erange = None
             self._xnorm64 = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
         self.cost_part = torch.zeros(self.aplan.grid, dtype=torch.float64, device=dev)
         if self.cplan.mode == "priv":
@@ -446,24 +259,16 @@ class LloydEngine:
             self.perm = torch.zeros(max(maxn, 1), dtype=torch.int32, device=dev)
             self.slots = K.seg_slots(self.cplan, d, dev)
         self.msg_len = k * d + k + 1
-        # incremental sums: sort regime with the centres in one LDS chunk (labels are final after one launch)
-        # (the device pruned step allocates its own, larger change lists in _pdev_alloc)
         self.delta = (K.DeltaState(max(maxn, 1), k, d, dp, self.row_chunks, self.msg_len, dev, self.aplan.grid,
-                                   fp8=fp8)
-                      if self._incremental and self.cplan.mode == "sort" and self.aplan.kc == self.aplan.kp
-                      and not (self.prune and pdev_ok) else None)
+                                   fp8=fp8) if want_delta else None)
         self.msgs = torch.zeros((self.row_chunks, self.msg_len), dtype=torch.float64, device=dev)
         self.cb = torch.zeros((self.kp, dp), dtype=torch.bfloat16, device=dev)
         self._cb_cost = torch.zeros_like(self.cb)  # centres of the last full/torch-pruned step's assignment
         self.cnorm = torch.zeros(self.kp, dtype=torch.float32, device=dev)
         self.shift2 = torch.zeros(k, dtype=torch.float64, device=dev)
         self._prev_centers = torch.zeros((k, d), dtype=torch.float64, device=dev) if self.spherical else None
-        # the device pruned step needs the K9r assign (every centre in one launch) and the sort-regime sums
-        if self.prune and pdev_ok:
-            self._pdev = True
+        if self._pdev:
             self._pdev_alloc()
-        elif self.prune:
-            self.use_graph, self.delta = False, None  # torch form: host-synchronised, its own sums
 
     def _set_mx(self) -> None:
         """Device max ||x||² over every rank (pruning slack), from the cached norms."""
@@ -484,8 +289,6 @@ class LloydEngine:
         mxv = self._pst.mx if self._pdev else None
         if mxv is not None:
             mxv.zero_()
-        if self._xnorm64 is None:
-            self._xnorm64 = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
         if n:
             for _, r0, r1, xc in self._x_chunks(whole=True):
                 K.row_pass(xc, r1 - r0, dp, self._xnorm[r0:r1], c0, c0n, None if cost is None else cost[r0:r1],
@@ -588,7 +391,7 @@ class LloydEngine:
                 st.force.fill_(1)
         elif self._pst is not None:  # bounds were relative to the old centres
             self._pst.valid = False
-            self._prune_centre_stats()
+            kmeans_prune_host._prune_centre_stats(self)
 
     # ------------------------------------------------------------------ iteration
     def step(self) -> None:
@@ -613,7 +416,7 @@ class LloydEngine:
             if self.track_prune:
                 self._pst.history.append(self._pdev_last())
         elif self.prune:
-            self._step_prune()
+            kmeans_prune_host._step_prune(self)
         elif self._wfast:
             self._step_weighted()
         elif self.gpu and self.use_graph and not self.comm.is_distributed:
@@ -642,13 +445,6 @@ class LloydEngine:
             return
         if self._wfast:  # double-double sums of the products need no grid
             return
-        if self._erange is None:  # norms came from a cache without the range: one more pass for it
-            er = torch.tensor([2 ** 31 - 1, -1], dtype=torch.int32, device=self.device)
-            if self.n:
-                tmp = torch.empty(self.n, dtype=torch.float32, device=self.device)
-                for _, r0, r1, xc in self._x_chunks(whole=True):
-                    K.row_pass(xc, r1 - r0, self.dp, tmp[r0:r1], erange=er)
-            self._erange = er
         if self._er_event is not None:  # prefetched behind the row pass (_prefetch_erange)
             self._er_event.synchronize()
             lo, hi = int(self._er_host[0]), int(self._er_host[1])
@@ -710,28 +506,26 @@ class LloydEngine:
             nrow = r1 - r0
             msg = self.msgs[c]
             if nrow > 0:
-                lab = self.labels[r0:r1]
-                if self.cplan.mode == "priv":
-                    K.assign_bf16(xc, nrow, self.dp, self.cb, self.cnorm, self.aplan, lab, self._best(r0, r1),
-                                  self.cost_part, xnorm=self.xnorm[r0:r1])
+                lab, dl = self.labels[r0:r1], self.delta
+                # (the sort regime's assign also emits the counting sort's histogram and ranks, and with
+                # incremental sums logs the label changes)
+                sort = self.cplan.mode != "priv"
+                rank = self.rank[r0:r1] if sort else None
+                K.assign_bf16(xc, nrow, self.dp, self.cb, self.cnorm, self.aplan, lab, self._best(r0, r1),
+                              self.cost_part, self.hist if sort else None, rank, xnorm=self.xnorm[r0:r1], delta=dl)
+                if not sort:
                     K.accumulate_priv(xc, nrow, lab, self.k, self.cplan, self.slab, self.cslab)
                     K.reduce_slabs(self.slab, self.cslab, self.cost_part, self.aplan.grid, self.k, self.d,
                                    self.cplan, msg)
-                elif self.delta is not None:
+                elif dl is not None:
                     # label changes logged by the assign; the gate picks the full or the delta accumulate
                     # on the device (no host sync, graph-capturable), both update delta.acc[c] -> msg
-                    rank, dl = self.rank[r0:r1], self.delta
-                    K.assign_bf16(xc, nrow, self.dp, self.cb, self.cnorm, self.aplan, lab, self._best(r0, r1),
-                                  self.cost_part, self.hist, rank, xnorm=self.xnorm[r0:r1], delta=dl)
                     dl.gate(c)
                     K.accumulate_sort(xc, nrow, self.dp, self.d, lab, rank, self.hist, self.aplan, self.k,
                                       self.cost_part, self.off, self.seg, self.perm, self.cplan, dl.acc[c],
                                       self.slots, gate=dl.mode[c], qscale=self._qscale)
                     dl.accumulate(xc, self.dp, lab, c, self.cost_part, self.aplan.grid, msg, qscale=self._qscale)
                 else:
-                    rank = self.rank[r0:r1]
-                    K.assign_bf16(xc, nrow, self.dp, self.cb, self.cnorm, self.aplan, lab, self._best(r0, r1),
-                                  self.cost_part, self.hist, rank, xnorm=self.xnorm[r0:r1])
                     K.accumulate_sort(xc, nrow, self.dp, self.d, lab, rank, self.hist, self.aplan, self.k,
                                       self.cost_part, self.off, self.seg, self.perm, self.cplan, msg, self.slots,
                                       qscale=self._qscale)
@@ -853,12 +647,7 @@ class LloydEngine:
             xb, ex = parts
             st = types.SimpleNamespace(xb=xb, ex=ex, dp=dp, split=False, tau=self.prune_tau(dp))
             st.xn = cached_row_sqnorm(xb, n, dp) if n else torch.zeros(1, dtype=torch.float32, device=dev)
-        st.rr_max = 0
-        for c in (320, 256, 192, 128, 64):
-            p = K.plan_assign(1, dp, c)
-            if p.rr_ct > 0 and p.kc == p.kp:
-                st.rr_max = c
-                break
+        st.rr_max = K.rr_max_chunk(dp)
         kp = round_up(max(st.rr_max, self.k), 32)
         st.cb = torch.zeros((kp, dp), dtype=torch.bfloat16, device=dev)
         st.cn = torch.zeros(kp, dtype=torch.float32, device=dev)
@@ -1354,15 +1143,8 @@ class LloydEngine:
         self._pdev_post()
 
     def _norms64(self) -> torch.Tensor:
-        """||x||² of the device rows summed in f64 (from the row pass; one more pass over X only when the
-        f32 norms came from a cache that did not keep them)."""
+        """||x||² of the device rows summed in f64 (from the row pass, or the feature tensor's cache)."""
         self._ensure_norms()
-        if self._xnorm64 is None:
-            self._xnorm64 = torch.empty(max(self.n, 1), dtype=torch.float64, device=self.device)
-            if self.n:
-                tmp = torch.empty(self.n, dtype=torch.float32, device=self.device)
-                for _, r0, r1, xc in self._x_chunks(whole=True):
-                    K.row_pass(xc, r1 - r0, self.dp, tmp[r0:r1], xn64=self._xnorm64[r0:r1])
         return self._xnorm64
 
     def _device_cost(self) -> torch.Tensor:
@@ -1438,253 +1220,6 @@ class LloydEngine:
     _PRUNE_TAU = 3e-5
     _PRUNE_CAP = 0.3  # a rank re-assigns all of its rows when more than this fraction are candidates
 
-    def _prune_init(self) -> None:
-        self._ensure_norms()
-        n, k, d, dev = self.n, self.k, self.d, self.device
-        bdt = torch.float32 if self.gpu else torch.float64
-        idt = torch.int32 if self.gpu else torch.int64
-        st = types.SimpleNamespace(valid=False, last=(True, 0), history=[])
-        st.ub = torch.full((max(n, 1),), float("inf"), dtype=bdt, device=dev)  # >= |x_i - c_label(i)|
-        st.lb = torch.zeros(max(n, 1), dtype=bdt, device=dev)  # <= distance to the nearest other centre
-        st.dmax = torch.zeros(3, dtype=bdt, device=dev)  # [largest drift, second largest, its index]
-        st.cand = torch.zeros(max(n, 1), dtype=idt, device=dev)
-        st.count = torch.zeros(1, dtype=idt, device=dev)
-        st.L = torch.zeros(k * d + 2 * k, dtype=torch.float64, device=dev)  # local [Σx | count | Σ|x|²] per centre
-        st.G = torch.zeros_like(st.L)  # all ranks' L summed (kept by adding the all-reduced deltas)
-        st.drift = torch.zeros(k, dtype=bdt, device=dev)
-        st.thr = torch.zeros(k, dtype=bdt, device=dev)
-        if self.gpu:
-            xn = self.xnorm[:n]
-        else:
-            self._xn64 = (self.x * self.x).sum(1)
-            xn = self._xn64
-        st.mx = self.comm.max_scalar(float(xn.max()) if n else 0.0)
-        if not self.gpu and self.labels is None:
-            self.labels = torch.zeros(max(n, 1), dtype=torch.int64)
-        self._pst = st
-
-    def _assign_centres64(self) -> torch.Tensor:
-        """The centres the assignment compares against (bf16-rounded on the GPU), as f64."""
-        return self.cb[: self.k, : self.d].to(torch.float64) if self.gpu else self.centers
-
-    def _prune_centre_stats(self, old: Optional[torch.Tensor] = None) -> None:
-        """drift[j] = |c_j - old_j| (rounded up) and thr[j] = half the distance from c_j to its nearest
-        other centre less the slack that keeps a pruned row's label strictly best under the full
-        assign's rounding: |x - c_j'|² - |x - c_j|² >= 4·s_j·(s_j - ub) >= 2·tau·(max|x|² + max|c|²)."""
-        st = self._pst
-        c = self._assign_centres64()
-        cn = (c * c).sum(1)
-        st.cn = cn
-        st.mc = float(cn.max()) if self.k else 0.0
-        st.c2 = 2.0 * self._tau * (st.mx + st.mc)
-        if old is not None:
-            dr = (c - old).pow(2).sum(1).sqrt() * (1.0 + 1e-6)
-            st.drift.copy_(dr)
-            top = torch.topk(dr, min(2, self.k))
-            st.dmax.copy_(torch.stack([top.values[0], top.values[-1],
-                                       top.indices[0].to(torch.float64)]).to(st.dmax.dtype))
-        if self.k > 1:
-            d2 = (cn[:, None] + cn[None, :] - 2.0 * (c @ c.T)).clamp_(min=0.0)
-            d2.fill_diagonal_(float("inf"))
-            half = 0.5 * d2.min(1).values.sqrt()
-            slack = self._tau * (st.mx + st.mc) / (2.0 * half)
-            thr = torch.where(half > 0, (half - slack) * (1.0 - 1e-6), torch.full_like(half, -math.inf))
-        else:
-            thr = torch.full((self.k,), math.inf, dtype=torch.float64, device=self.device)
-        st.thr.copy_(thr)
-
-    def _prune_bound(self, best: torch.Tensor, xn: torch.Tensor) -> torch.Tensor:
-        """Upper bound on the exact distance from the assign's squared distance (rounded up)."""
-        return (best.clamp(min=0) + self._tau * (xn + self._pst.mc)).sqrt() * (1.0 + 1e-6)
-
-    def _prune_lower(self, xg: torch.Tensor, xng: torch.Tensor, lab: torch.Tensor, out: torch.Tensor,
-                     chunk: Optional[int] = None) -> None:
-        """out[i] = lower bound on the distance from row i to its nearest centre other than lab[i].
-        GPU: one bf16 GEMM against the centres with f32 accumulation and f32 output (hipBLASLt), the
-        label's column masked, min over centres; its rounding is that of the full assign, covered
-        by subtracting tau·(|x|² + max|c|²) before the square root. CPU: the same in f64."""
-        st, k = self._pst, self.k
-        if self.gpu:
-            cbt = self.cb[:k].t()
-            cn = st.cn.to(torch.float32)
-        else:
-            cbt = self.centers.t()
-            cn = st.cn
-        if chunk is None:  # [chunk, k] f32 blocks (CML_PRUNE_CHUNK_MB, default 512 MiB)
-            chunk = max(1024, (int(os.environ.get("CML_PRUNE_CHUNK_MB", 512)) << 20) // (4 * max(k, 1)))
-        for s0 in range(0, xg.shape[0], chunk):
-            xc = xg[s0:s0 + chunk]
-            xn = xng[s0:s0 + chunk].to(cn.dtype)
-            if k > 1:
-                if self.gpu:
-                    if xc.dtype != torch.bfloat16:
-                        xc = xc.to(torch.bfloat16)
-                    # |c_j|² - 2 x·c_j with the bias and scale in the GEMM epilogue (one f32 write)
-                    dist = torch.addmm(cn, xc, cbt, out_dtype=torch.float32, alpha=-2.0)
-                    if k % 4 == 0 and out.dtype == torch.float32:  # masked row min + bound in one pass
-                        labc = lab[s0:s0 + chunk]
-                        labc = labc if labc.dtype == torch.int32 else labc.to(torch.int32)
-                        K.prune_lower(dist, labc.contiguous(), xn.contiguous(), st.mc, self._tau,
-                                      out[s0:s0 + chunk])
-                        continue
-                else:
-                    dist = torch.addmm(cn, xc, cbt, alpha=-2.0)
-                dist.scatter_(1, lab[s0:s0 + chunk].long()[:, None], math.inf)
-                sec = dist.min(1).values + xn
-            else:
-                sec = torch.full_like(xn, math.inf)
-            lo = (sec - self._tau * (xn + st.mc)).clamp_(min=0.0).sqrt_().mul_(1.0 - 1e-6)
-            out[s0:s0 + chunk] = lo.to(out.dtype)
-
-    @staticmethod
-    def _moved_sums(delta: torch.Tensor, k: int, d: int, xs: torch.Tensor, xq: torch.Tensor, new: torch.Tensor,
-                    old: torch.Tensor, chunk: int = 1 << 17, split: int = 64) -> None:
-        """delta += the per-centre [Σx | count | Σ|x|²] change of rows moving old -> new: an f64 GEMM of
-        a {-1, 0, +1} move matrix with [x | 1 | |x|²] (sums of bf16 / fp8 rows are exact in f64, so the
-        result does not depend on the summation order; scatter-add atomics onto k rows serialise). The
-        row dimension is split into ``split`` batches so the tiny k x (d + 2) output still spreads over
-        every CU (one plain GEMM ran 4 workgroups: 14 ms per 128K rows)."""
-        kd = k * d
-        for s0 in range(0, xs.shape[0], chunk):
-            nw, o = new[s0:s0 + chunk], old[s0:s0 + chunk]
-            c = nw.shape[0]
-            b = max(1, min(split, c // 256))
-            cp = -(-c // b) * b
-            w = torch.zeros((cp, k), dtype=torch.float64, device=xs.device)
-            ar = torch.arange(c, device=xs.device)
-            w[ar, nw] = 1.0
-            w[ar, o] = -1.0
-            v = torch.zeros((cp, d + 2), dtype=torch.float64, device=xs.device)
-            v[:c, :d] = xs[s0:s0 + chunk]
-            v[:c, d] = 1.0
-            v[:c, d + 1] = xq[s0:s0 + chunk]
-            part = torch.bmm(w.view(b, cp // b, k).transpose(1, 2), v.view(b, cp // b, d + 2)).sum(0)
-            delta[:kd].view(k, d).add_(part[:, :d])
-            delta[kd:kd + k].add_(part[:, d])
-            delta[kd + k:].add_(part[:, d + 1])
-
-    def _step_prune(self) -> None:
-        """One exact Lloyd iteration: bounds pass (K9p), the rows it cannot prove are gathered and
-        assigned against every centre (K9), the per-centre sums move by the rows whose label changed,
-        and the deltas are all-reduced. A rank whose candidates exceed _PRUNE_CAP of its rows, or
-        whose bounds are stale (first step, set_centers), assigns all of its rows instead; the
-        collective sequence is the same either way."""
-        if self._pst is None:
-            self._prune_init()
-            self._prune_centre_stats()
-        st = self._pst
-        n, k, d = self.n, self.k, self.d
-        full, m = not st.valid, n
-        if not full and n:
-            with trace("prune.bounds"):
-                K.prune_bounds(self.labels[:n], st.ub, st.lb, st.drift, st.dmax, st.thr, st.c2, k, st.cand,
-                               st.count)
-                m = int(st.count[0].item())
-            full = m > self._PRUNE_CAP * n
-        with trace("prune.full" if full else "prune.candidates"):
-            delta = self._prune_local_full() if full else self._prune_local_cands(m)
-        st.last = (full, m)
-        st.history.append((bool(full), int(m)))
-        with trace("prune.allreduce_update"):
-            self._prune_apply(delta)
-
-    def _prune_apply(self, delta: torch.Tensor) -> None:
-        st = self._pst
-        k, d = self.k, self.d
-        self.comm.allreduce_(delta)
-        st.G += delta
-        kd = k * d
-        c = self._assign_centres64()
-        s_, cnt, q = st.G[:kd].view(k, d), st.G[kd:kd + k], st.G[kd + k:]
-        # cost of this assignment: Σ_j Σ_{i in j} |x_i - c_j|² = Σ_j (Q_j - 2 c_j·S_j + n_j |c_j|²)
-        cost = (q.sum() - 2.0 * (c * s_).sum() + (cnt * st.cn).sum()).clamp(min=0.0)
-        msg = torch.cat([st.G[:kd + k], cost.reshape(1)])
-        old = c.clone()
-        if self.gpu:
-            self._cb_cost.copy_(self.cb)  # exact cost on first read (the expanded form above cancels)
-            self._update_gpu(msg.view(1, -1))
-            self._cost_fn = self._exact_cost
-        else:
-            self._update_cpu(msg)
-        st.valid = True
-        with trace("prune.centre_stats"):
-            self._prune_centre_stats(old)
-
-    def _prune_local_full(self) -> torch.Tensor:
-        st = self._pst
-        n, k, d = self.n, self.k, self.d
-        kd = k * d
-        new = torch.zeros_like(st.L)
-        if n and self.gpu:
-            msg, xc, lab, best = self.msgs[0], self.x[:n], self.labels[:n], self.best[:n]
-            if self.cplan.mode == "priv":
-                K.assign_bf16(xc, n, self.dp, self.cb, self.cnorm, self.aplan, lab, best, self.cost_part,
-                              xnorm=self.xnorm[:n])
-                K.accumulate_priv(xc, n, lab, k, self.cplan, self.slab, self.cslab)
-                K.reduce_slabs(self.slab, self.cslab, self.cost_part, self.aplan.grid, k, d, self.cplan, msg)
-            else:
-                rank = self.rank[:n]
-                K.assign_bf16(xc, n, self.dp, self.cb, self.cnorm, self.aplan, lab, best, self.cost_part,
-                              self.hist, rank, xnorm=self.xnorm[:n])
-                K.accumulate_sort(xc, n, self.dp, d, lab, rank, self.hist, self.aplan, k, self.cost_part,
-                                  self.off, self.seg, self.perm, self.cplan, msg, self.slots)
-            new[:kd + k] = msg[:kd + k]
-            new[kd + k:] = group_reduce(lab, self.xnorm[:n], k, "sum")
-            st.ub[:n] = self._prune_bound(best, self.xnorm[:n])
-            self._prune_lower(xc, self.xnorm[:n], lab, st.lb)
-        elif n:
-            lab, best = K.assign_reference(self.x, self.centers)
-            self.labels = lab
-            sums, counts = K.sums_reference(self.x, lab, k)
-            new[:kd] = sums.reshape(-1)
-            new[kd:kd + k] = counts
-            new[kd + k:].index_add_(0, lab, self._xn64)
-            st.ub[:n] = self._prune_bound(best, self._xn64)
-            self._prune_lower(self.x, self._xn64, lab, st.lb)
-        delta = new - st.L
-        st.L = new
-        return delta
-
-    def _prune_local_cands(self, m: int) -> torch.Tensor:
-        st = self._pst
-        k, d = self.k, self.d
-        delta = torch.zeros_like(st.L)
-        if m == 0:
-            return delta
-        cand = st.cand[:m].long()
-        with trace("prune.gather_assign"):
-            xg, xng, labg, bestg = self._prune_assign_rows(cand, m)
-        old = self.labels[cand]
-        labg = labg.to(old.dtype)
-        self.labels[cand] = labg
-        st.ub[cand] = self._prune_bound(bestg, xng).to(st.ub.dtype)
-        lo = torch.empty(m, dtype=st.lb.dtype, device=self.device)
-        with trace("prune.lower"):
-            self._prune_lower(xg, xng, labg, lo)
-        st.lb[cand] = lo
-        with trace("prune.delta"):
-            ch = torch.nonzero(labg != old).flatten()
-            if ch.numel():
-                o, nw = old[ch].long(), labg[ch].long()
-                self._moved_sums(delta, k, d, xg[ch, :d].to(torch.float64), xng[ch].to(torch.float64), nw, o)
-        st.L += delta
-        return delta
-
-    def _prune_assign_rows(self, cand: torch.Tensor, m: int):
-        """Gathered candidate rows, their |x|², labels and squared distances against every centre."""
-        k = self.k
-        if self.gpu:
-            fp8 = K.is_fp8(self.x)
-            xg = self.x.view(torch.uint8)[cand].view(self.x.dtype) if fp8 else self.x[cand]
-            xng = self.xnorm[cand]
-            labg = torch.empty(m, dtype=torch.int32, device=self.device)
-            bestg = torch.empty(m, dtype=torch.float32, device=self.device)
-            plan = K.plan_assign(m, self.dp, k, self.device.index or 0, fp8=fp8)
-            K.assign_bf16(xg, m, self.dp, self.cb, self.cnorm, plan, labg, bestg, None, xnorm=xng)
-        else:
-            xg, xng = self.x[cand], self._xn64[cand]
-            labg, bestg = K.assign_reference(xg, self.centers)
-        return xg, xng, labg, bestg
 
     def prune_stats(self) -> dict:
         """Last pruned step: whether this rank re-assigned all rows, and how many it re-assigned."""
@@ -1894,223 +1429,10 @@ class LloydEngine:
 
     # ------------------------------------------------------------------ initialisation
     def init_random(self, seed: int) -> np.ndarray:
-        """Spark initMode="random": k distinct rows sampled uniformly without replacement."""
-        ids = self.row_ids()
-        u = rng.uniform(ids, seed, stream=11)
-        take = min(self.k, self.n)
-        loc_u, loc_i = torch.topk(-u, take) if take > 0 else (u[:0], ids[:0].long())
-        cand_u = -loc_u
-        rows = self._rows_f64(loc_i)
-        all_u = self.comm.allgather_cat(cand_u.to(torch.float64))
-        all_rows = self.comm.allgather_cat(rows)
-        order = torch.argsort(all_u)[: self.k]
-        return all_rows[order].cpu().numpy()
-
-    def _rows_f64(self, idx: torch.Tensor) -> torch.Tensor:
-        if self._hs is not None:  # host rows
-            return self.x[idx.long().cpu(), : self.d].to(torch.float64).to(self.device)
-        if self.gpu:
-            return self.x[idx.long(), : self.d].to(torch.float64)
-        return self.x[idx.long()].to(torch.float64)  # (the screen keeps f32 source rows)
-
-    def _min_dist_idx(self, cands: torch.Tensor):
-        """(squared distance to the nearest of `cands` as f64, its index) of every local row."""
-        if self._screen:
-            return self._screen_min_dist(cands)
-        if not self.gpu:
-            lab, best = K.assign_reference(self.x, cands)
-            return best, lab
-        self._ensure_norms()
-        lab, best = self._assign_all(cands)
-        return best.to(torch.float64), lab.long()
+        return kmeans_init.init_random(self, seed)
 
     def init_kmeans_parallel(self, seed: int, steps: int = 2, as_device: bool = False):
-        """k-means|| (Bahmani et al.), Spark's default initMode (initSteps rounds sampling each row with
-        probability 2k·cost/Σcost), then weighted local k-means++ + Lloyd on the distinct candidates.
-
-        GPU ranks stay on the device: the first pass over X computes the row norms and the costs
-        against the first centre together (K12 row pass), a round samples with one kernel over the
-        costs, the new candidates' distances run on K9r in chunks of at most 256 centres merged into
-        (cost, nearest candidate), and the local k-means runs as HIP kernels. The nearest candidate of
-        every row is carried across rounds (strict improvement keeps the earlier candidate: argmin's
-        first-index rule over the concatenated list), so the candidate weights need no extra pass.
-        The GPU path reads the host only where a size decides the next launches: once per round (the
-        sampled counts of every rank, one fixed-size all-gather) plus the pruned pass's row counts, the
-        distinct-candidate count and the result — the first centre, Σcost and the sampling rate, the
-        candidate weights and the local Lloyd's convergence stay on the device (~11 ms of
-        init at the 8-GPU shard was mostly host round trips).
-        The CPU path runs the same algorithm in f64, with the same distinct-candidate order (sorted
-        rows) and the bitwise-identical local k-means (host twin of the kernels). ``as_device``: return
-        the centres as the f64 device tensor (GPU engines; set_centers takes it without a host copy)."""
-        if self.gpu:
-            return self._init_kmeans_parallel_gpu(seed, steps, as_device)
-        k = self.k
-        ids = self.row_ids()
-        gn = self.global_n
-        if gn == 0:
-            raise ValueError("KMeans on an empty dataset")
-        # first centre: one uniformly drawn global row (same draw on every rank)
-        u = rng.uniform(ids, seed, stream=1)
-        lu, li = (torch.min(u, 0) if self.n else (torch.tensor(2.0, device=self.device), torch.tensor(0)))
-        first_u = self.comm.allgather_cat(lu.reshape(1).to(torch.float64))
-        owner = int(torch.argmin(first_u).item())
-        row = self._rows_f64(li.reshape(1)) if self.n else torch.zeros((1, self.d), dtype=torch.float64,
-                                                                      device=self.device)
-        row = self.comm.allgather(row)[owner] if self.comm.is_distributed else row
-        centers = [row.reshape(1, self.d)]
-        if self.n:
-            costs, nearest = self._min_dist_idx(centers[0])
-        else:
-            costs = torch.zeros(0, dtype=torch.float64, device=self.device)
-            nearest = torch.zeros(0, dtype=torch.int64, device=self.device)
-        ncand = 1
-        for step in range(steps):
-            local = float(costs[: self.n].sum(dtype=torch.float64).item()) if self.n else 0.0
-            sum_cost = self.comm.sum_scalar(local)
-            if sum_cost <= 0:
-                break
-            us = rng.uniform(ids, seed, stream=100 + step)  # the sample kernel's test: u < scale·cost
-            chosen = torch.nonzero(us < (2.0 * k / sum_cost) * costs).flatten()
-            new = self._rows_f64(chosen) if chosen.numel() else torch.zeros((0, self.d), dtype=torch.float64,
-                                                                            device=self.device)
-            new = self.comm.allgather_cat(new)
-            if new.shape[0] == 0:
-                continue
-            centers.append(new)
-            if self.n:
-                d_new, i_new = self._min_dist_idx(new)
-                better = d_new < costs
-                costs = torch.where(better, d_new, costs)
-                nearest = torch.where(better, i_new + ncand, nearest)
-            ncand += new.shape[0]
-        return self._init_finish(seed, centers, costs, nearest, as_device=False)
-
-    def _init_kmeans_parallel_gpu(self, seed: int, steps: int, as_device: bool):
-        with trace("kinit.gpu"):
-            return self._init_kmeans_parallel_gpu_body(seed, steps, as_device)
-
-    def _init_kmeans_parallel_gpu_body(self, seed: int, steps: int, as_device: bool):
-        k, n, d, dev, comm = self.k, self.n, self.d, self.device, self.comm
-        ids = self.row_ids()
-        ids64 = ids if ids.dtype == torch.int64 and ids.is_contiguous() else ids.to(torch.int64).contiguous()
-        # first centre: the global row with the smallest counter uniform — one fixed-size all-gather of
-        # [u_min, local rows, row] per rank, picked on the device (no host read)
-        u = rng.uniform(ids, seed, stream=1)
-        if n:
-            lu, li = torch.min(u, 0)
-            row = self._rows_f64(li.reshape(1)).reshape(-1)
-        else:
-            lu = torch.full((), 2.0, dtype=torch.float64, device=dev)
-            row = torch.zeros(d, dtype=torch.float64, device=dev)
-        hdr = torch.cat([lu.reshape(1).to(torch.float64),
-                         torch.full((1,), float(n), dtype=torch.float64, device=dev), row])
-        g = comm.allgather_fixed(hdr)
-        gn_dev = g[:, 1].sum()
-        # every candidate of every round lands in one f64 buffer, in Spark's order (first centre, then each
-        # round's rows by rank and row id): the rounds and the finish read views of it, no concatenations
-        cap = min(max(n, 1), max(4096, 8 * k))
-        cands = torch.empty((1 + steps * 2 * cap if comm.is_distributed else 1 + steps * cap, d), dtype=torch.float64,
-                            device=dev) if steps <= 4 else None
-        if cands is None or cands.shape[0] > 65536:  # (many init steps: grow on demand instead)
-            cands = torch.empty((1 + 4 * k + 1024, d), dtype=torch.float64, device=dev)
-        cands[0].copy_(g[torch.argmin(g[:, 0]), 2:])
-        c0 = cands[0:1]
-        costs, nearest = self._init_first_pass(c0)
-        xmax = self._xmax_dev()
-        ncand = 1
-        two_k = self._const([0.0, 2.0 * k], torch.float64)
-        out = torch.empty(cap, dtype=torch.int32, device=dev)
-        send = torch.empty((cap, d), dtype=torch.float64, device=dev) if comm.is_distributed else None
-        cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-        head = torch.empty(2, dtype=torch.float64, device=dev)
-        for step in range(steps):
-            tr = trace(f"kinit.round{step}")
-            tr.__enter__()
-            # Σcost over every rank and the rate 2k / Σcost stay on the device (the sample kernel forms it)
-            # (Σcost as integer limbs on the grid of 5·max||x||² — a row's squared distance to a candidate row is at
-            # most 4·max||x||², plus the bf16 / MX rounding of the candidate — so the rate is the same bits for
-            # any split of the rows over ranks: exactsum.hip)
-            scale = two_k.clone()
-            limbs = torch.zeros(2, dtype=torch.int64, device=dev)
-            if n:
-                K.fixsum(costs, n, xmax, 5.0, limbs=limbs)
-            comm.allreduce_(limbs)
-            K.fixsum_finalize(limbs, 1, xmax, 5.0, out=scale[0:1])
-            cnt.zero_()
-            if cands.shape[0] < ncand + (cap if send is None else 0):
-                cands = self._grow_cands(cands, ncand, ncand + cap)
-            gathered = False
-            if n:
-                K.init_sample(costs, ids64, n, rng.key(seed, 100 + step), scale, out, cnt)
-                # the sampled rows in row order, widened to f64, before the host read (device count)
-                if self._hs is None:  # (host rows of an out-of-core engine: the gather below)
-                    gathered = K.gather_rank_rows(self.x, out, cnt, cap, d, cands[ncand:] if send is None else send)
-            # the one host read of the round: every rank's sampled count (and, once, the global row count)
-            head[0:1].copy_(cnt)
-            head[1:2].copy_(gn_dev.reshape(1))
-            hv = comm.allgather_fixed(head).cpu()
-            counts = [int(v) for v in hv[:, 0].tolist()]
-            if step == 0:
-                self._gn = int(hv[0, 1].item())
-                if self._gn == 0:
-                    raise ValueError("KMeans on an empty dataset")
-            m = counts[comm.rank]
-            if m > cap:  # rare: more than the expected ~2k·(share of the cost) rows; sample again with room
-                out = torch.empty(m, dtype=torch.int32, device=dev)
-                cnt.zero_()
-                K.init_sample(costs, ids64, n, rng.key(seed, 100 + step), scale, out, cnt)
-                cap, gathered = m, False
-            mt = sum(counts)
-            if cands.shape[0] < ncand + mt:
-                cands = self._grow_cands(cands, ncand, ncand + mt)
-            dst = send if send is not None else cands[ncand:]
-            if m and not gathered:
-                chosen = torch.sort(out[:m]).values.long()
-                if send is not None and send.shape[0] < m:
-                    send = dst = torch.empty((m, d), dtype=torch.float64, device=dev)
-                dst[:m].copy_(self._rows_f64(chosen))
-            if send is not None:
-                pad = max(max(counts), 1)
-                if send.shape[0] < pad:  # (a small shard's buffer is sized by its own rows: every rank sends pad)
-                    grown = torch.zeros((pad, d), dtype=torch.float64, device=dev)
-                    grown[:m].copy_(send[:m])
-                    send = grown
-                gath = comm.allgather_fixed(send[:pad])
-                at = ncand
-                for r in range(comm.world_size):
-                    if counts[r]:
-                        cands[at:at + counts[r]].copy_(gath[r, :counts[r]])
-                    at += counts[r]
-            if mt == 0:
-                tr.__exit__(None, None, None)
-                continue
-            new = cands[ncand:ncand + mt]
-            # bf16 copies and norms of every new candidate in one K11 launch; each K9r chunk is a view of them
-            # (rows past mt: zero centres with +inf norms, which no row takes)
-            dp = self.dp
-            kp_all = round_up(mt, 64)
-            cbn = torch.empty((kp_all, dp), dtype=torch.bfloat16, device=dev)
-            cnn = torch.empty(kp_all, dtype=torch.float32, device=dev)
-            K.update_centers(None, mt, d, new, cbn, dp, kp_all, cnn, None, snap=self._mx)
-            # once most rows sit near a candidate, only the new candidates close to a row's nearest one
-            # can take it over (_init_candidate_pass_pruned): the second round at once; in the first
-            # round (only the first centre so far) everything after the first K9r chunk
-            first = self._first_chunk(mt) if step == 0 else 0
-            if first:
-                self._init_candidate_pass(first, cbn, cnn, 0, costs, nearest, ncand)
-            if mt > first and not self._init_candidate_pass_pruned(
-                    cands[:ncand + first], new[first:], cbn, cnn, first, costs, nearest, ncand + first):
-                self._init_candidate_pass(mt - first, cbn, cnn, first, costs, nearest, ncand + first)
-            ncand += mt
-            tr.__exit__(None, None, None)
-        with trace("kinit.finish"):
-            return self._init_finish(seed, cands[:ncand], costs, nearest, as_device=as_device)
-
-    @staticmethod
-    def _grow_cands(cands: torch.Tensor, used: int, need: int) -> torch.Tensor:
-        out = torch.empty((max(need, 2 * cands.shape[0]), cands.shape[1]), dtype=cands.dtype, device=cands.device)
-        out[:used].copy_(cands[:used])
-        return out
+        return kmeans_init.init_kmeans_parallel(self, seed, steps, as_device)
 
     def _const(self, values, dtype) -> torch.Tensor:
         """A small device tensor of host values without a blocking copy (pinned staging, non_blocking): a
@@ -2118,245 +1440,6 @@ class LloydEngine:
         fit's hot path stalled the host behind the row pass (profiles/r5/shard/)."""
         h = torch.tensor(values, dtype=dtype, pin_memory=self.device.type == "cuda")
         return h.to(self.device, non_blocking=True)
-
-    def _init_finish(self, seed: int, centers: list, costs: torch.Tensor, nearest: torch.Tensor, as_device: bool):
-        """Distinct candidates, their weights (rows per candidate, all-reduced) and the local k-means."""
-        k = self.k
-        cand = centers if torch.is_tensor(centers) else torch.cat(centers, 0)
-        # distinct candidates in sorted-row order (np.unique's order; identical on every device)
-        uniq, inverse = K.unique_rows(cand) if cand.is_cuda else torch.unique(cand, dim=0, return_inverse=True)
-        if uniq.shape[0] <= k:
-            out = uniq
-        else:
-            if self.n and self.w is not None:
-                # summed row weights per candidate (deterministic f64 sums, as the Lloyd sums)
-                w = K.sums_reference(self.w[:, None], inverse.reshape(-1)[nearest[: self.n].long()],
-                                     uniq.shape[0])[0][:, 0].contiguous()
-            elif self.n:
-                # rows per candidate (an int32 histogram of the nearest ids: integer counts, exact in any
-                # order), folded onto the distinct candidates
-                if self.gpu or nearest.is_cuda:  # device rows (bf16 path or the screen): no bincount sync
-                    per_i = torch.zeros(cand.shape[0], dtype=torch.int32, device=self.device)
-                    near32 = nearest if nearest.dtype == torch.int32 else nearest[: self.n].to(torch.int32)
-                    K.int_hist(near32.contiguous(), self.n, cand.shape[0], per_i)
-                    per = per_i.to(torch.float64)
-                else:
-                    per = torch.bincount(nearest[: self.n], minlength=cand.shape[0]).to(torch.float64)
-                w = torch.zeros(uniq.shape[0], dtype=torch.float64, device=self.device)
-                w.index_add_(0, inverse.reshape(-1), per)
-            else:
-                w = torch.zeros(uniq.shape[0], dtype=torch.float64, device=self.device)
-            self.comm.allreduce_(w)
-            # unweighted: the weights are row counts summing to the global row count, which is positive
-            # (the candidates are rows), so local_kmeans skips its clamp and all-zero fallback
-            out = K.local_kmeans(uniq, w, k, seed, max_iter=30, spherical=self.spherical, counts=self.w is None)
-            if self.comm.is_distributed:
-                # every rank ran the same local k-means on the same candidates and weights; rank 0's
-                # result is taken verbatim (one source of truth for the centres every rank starts from)
-                out = self.comm.broadcast_(out.contiguous(), 0)
-        nk = int(out.shape[0])
-        if nk < k:
-            # Spark may return fewer centres when there are < k distinct points; pad by repetition so the
-            # device buffers keep their shape, and record the real count.
-            self.k_effective = nk
-            out = torch.cat([out, out[-1:].expand(k - nk, -1)], 0)
-        else:
-            self.k_effective = k
-        out = out.to(torch.float64).contiguous()
-        if self._pdev and self.n and self.k_effective == k and os.environ.get("CML_KMEANS_SEED_BOUNDS", "1") != "0":
-            # what the first Lloyd step needs to start from bounds instead of a full pass (set_centers)
-            self._seed = types.SimpleNamespace(nearest=nearest, costs=costs, inverse=inverse, uniq=uniq, out=out,
-                                               out_np=None)
-        if as_device and self.gpu:
-            return out
-        res = out.cpu().numpy()
-        if self._seed is not None and self._seed.out is out:
-            self._seed.out_np = res
-        return res
-
-    def _init_first_pass(self, c0: torch.Tensor):
-        """(cost f32, nearest i32) of every local row against the first centre, from the row pass that
-        also fills the norms (one read of X; a second read only if the norms were cached already). The
-        centre's bf16 norm reaches the kernel on the device."""
-        n, d, dp, dev = self.n, self.d, self.dp, self.device
-        # K11 writes every row of the 32-row block (zero rows, +inf norms past the first) and rewrites the
-        # f64 centre with its own value: no clears, no copy of c0
-        cb0 = torch.empty((32, dp), dtype=torch.bfloat16, device=dev)
-        cn0 = torch.empty(32, dtype=torch.float32, device=dev)
-        c0 = c0.reshape(1, d)
-        if c0.dtype != torch.float64 or not c0.is_contiguous():
-            c0 = c0.to(torch.float64).contiguous()
-        K.update_centers(None, 1, d, c0, cb0, dp, 32, cn0, None, snap=self._mx)
-        alloc = torch.empty if n else torch.zeros  # (the row pass writes every row's cost and nearest)
-        costs = alloc(max(n, 1), dtype=torch.float32, device=dev)
-        nearest = alloc(max(n, 1), dtype=torch.int32, device=dev)
-        self._row_pass(cb0[0].to(torch.float32).contiguous(), 0.0, costs, nearest, c0n_dev=cn0[0:1])
-        return costs, nearest
-
-    def _init_scratch(self):
-        """Per-engine scratch of the k-means|| candidate passes (allocated once; the K9r passes write every
-        entry they read back, so nothing is cleared per round)."""
-        sc = self._iscr
-        if sc is None:
-            n, dev = self.n, self.device
-            tr = self.aplan.round_rows
-            sc = types.SimpleNamespace()
-            sc.lab = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-            sc.best = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-            sc.list_a = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
-            # list B is read in whole K9r tiles: entries past the count must be valid row ids (zeros once)
-            sc.list_b = torch.zeros(n + tr, dtype=torch.int32, device=dev)
-            sc.cxn = torch.zeros(n + tr, dtype=torch.float32, device=dev)
-            sc.lab_in = torch.full((n + tr,), -1, dtype=torch.int32, device=dev)
-            sc.cnt = torch.zeros(2, dtype=torch.int32, device=dev)
-            self._iscr = sc
-        return sc
-
-    def _init_candidate_pass(self, m: int, cbn: torch.Tensor, cnn: torch.Tensor, c_off: int, costs: torch.Tensor,
-                             nearest: torch.Tensor, off: int) -> None:
-        """Merge the distances to the candidates cbn[c_off : c_off + m] (bf16 copies, norms cnn; K9r, at
-        most 320 centres per launch) into (cost, nearest); candidate i is global index off + i."""
-        n, dp, dev = self.n, self.dp, self.device
-        if n == 0:
-            return
-        sc = self._init_scratch()
-        lab, best = sc.lab[:n], sc.best[:n]
-        xn = self.xnorm
-        parts, c0 = [], 0
-        for size in self._candidate_chunks(m):
-            kp = round_up(size, 32)
-            parts.append((c0, size, cbn[c_off + c0:c_off + c0 + kp], cnn[c_off + c0:c_off + c0 + kp]))
-            c0 += size
-        # rows outer (one read of X per pass, streamed out of core), candidate chunks inner: the merges
-        # of a row run in candidate order either way
-        for _, r0, r1, xc in self._x_chunks(whole=True):
-            mm = r1 - r0
-            if mm == 0:
-                continue
-            for c0, kc, cb, cn in parts:
-                plan = K.plan_assign(mm, dp, kc, dev.index or 0, fp8=K.is_fp8(self.x))
-                K.assign_bf16(xc, mm, dp, cb, cn, plan, lab[r0:r1], best[r0:r1], None, xnorm=xn[r0:r1])
-                K.init_merge(costs[r0:r1], nearest[r0:r1], best[r0:r1], lab[r0:r1], off + c0, mm)
-
-    _INIT_LMAX = 8  # relevant new candidates a row may have to take the per-row path (else the K9r pass)
-
-    def _init_candidate_pass_pruned(self, prev: torch.Tensor, new: torch.Tensor, cbn: torch.Tensor,
-                                    cnn: torch.Tensor, c_off: int, costs: torch.Tensor, nearest: torch.Tensor,
-                                    off: int) -> bool:
-        """A k-means|| candidate pass that skips what the triangle inequality rules out: a row at distance
-        r from its nearest candidate p can only move to a new candidate y with |p - y| < 2r. With the
-        distances from every existing candidate to the new ones sorted (a small f64 table), each row
-        counts its relevant candidates (kmeans init_classify); rows with none are done, rows with at
-        most _INIT_LMAX get those distances from a per-row kernel, the rest run the K9r candidate pass
-        over their positions (mode 2). Same nearest candidates as the full pass up to the rounding of
-        near-ties. No host read: the list sizes stay on the device (the launches are sized by capacity).
-        ``new`` (f64) are the candidates whose bf16 copies / norms are cbn / cnn[c_off:]; candidate i is
-        global index off + i. Returns False (nothing changed) when the pruned pass does not apply (host rows,
-        pruning off)."""
-        n, d, dp, dev = self.n, self.d, self.dp, self.device
-        # default on up to Dp = 256; at Dp = 512 the per-row path reads 1 KiB of candidate per listed
-        # candidate and the gathered K9r pass loses to the streaming one: the config-5 pipeline's init
-        # (125M x 512 fp8, k = 128) ran 120 ms pruned vs 97.5 ms full (profiles/r4/pipeline_init_ab.log)
-        mode = os.environ.get("CML_KMEANS_INIT_PRUNE", "auto")
-        if mode == "0" or (mode == "auto" and dp > 256):
-            return False
-        if not self._pdev or not self._rr_max_chunk():
-            return False
-        if n == 0:
-            return True
-        m = int(new.shape[0])
-        tab = K.init_table(prev, new)  # one launch: direct-difference distances, sorted in LDS
-        if tab is not None:
-            tab_v, tab_j, pn32 = tab
-        else:
-            P = prev.to(device=dev, dtype=torch.float64)
-            Y = new.to(device=dev, dtype=torch.float64)
-            pn, yn = (P * P).sum(1), (Y * Y).sum(1)
-            d2 = pn[:, None] + yn[None, :] - 2.0 * (P @ Y.T)
-            eps = 1e-12 * (pn.max() + yn.max())  # device scalar (no host read)
-            vals, order = torch.sort((d2 - eps).clamp_(min=0.0).sqrt_().mul_(1.0 - 1e-6), dim=1)
-            tab_v = vals.to(torch.float32).contiguous()
-            tab_j = order.to(torch.int32).contiguous()
-            pn32 = (pn * (1.0 + 1e-6)).to(torch.float32).contiguous()
-        tau = 2.0 * self._tau
-        sc = self._init_scratch()
-        list_a, list_b, cnt = sc.list_a, sc.list_b, sc.cnt
-        cnt.zero_()
-        # per-row path limit: each listed candidate costs the row a read of its dp-wide bf16 copy from L2
-        # (1 KiB at dp = 512), so wide rows hand longer lists to the MFMA pass sooner
-        lmax = int(os.environ.get("CML_KMEANS_INIT_LMAX", self._INIT_LMAX if dp <= 256 else 4))
-        lmax = max(0, min(self._INIT_LMAX, lmax))
-        K.init_classify(costs, nearest, self.xnorm, pn32, tab_v, tau, n, lmax, list_a, cnt[0:1], list_b, cnt[1:2])
-        # no host read of the list sizes: the per-row kernel and the K9r candidate pass take them from the
-        # device and size their grids by the capacity (dead tiles exit at once); the new candidates' bf16
-        # rows are the K11 copies the K9r chunks use
-        K.init_near_list(self.x, dp, costs, nearest, self.xnorm, pn32, tab_v, tab_j, cbn[c_off:c_off + m], off, tau,
-                         list_a, cnt[0:1], n)
-        st = self._pst
-        cxn = sc.cxn
-        torch.index_select(self.xnorm[:n], 0, list_b[:n], out=cxn[:n])  # entries past the count: row 0's, unread
-        c0 = 0
-        for size in self._candidate_chunks(m):
-            kp = round_up(size, 32)
-            cbk, cnk = cbn[c_off + c0:c_off + c0 + kp], cnn[c_off + c0:c_off + c0 + kp]
-            plan = K.plan_assign(n, dp, size, dev.index or 0, fp8=K.is_fp8(self.x))
-            mc = cnk[:size].max().reshape(1)
-            K.assign_rr_ext(2, self.x, n, dp, cbk, cnk, plan, cxn, self.labels, None, st.ub, st.lb, mc,
-                            self._tau, idx=list_b, n_dev=cnt[1:2], lab_in=sc.lab_in, merge_cost=costs,
-                            merge_near=nearest, merge_off=off + c0)
-            c0 += size
-        if self.track_prune:
-            ca, cb = (int(v) for v in cnt.tolist())
-            self._init_prune_history.append((n, ca, cb))
-        return True
-
-    # Time of one K9r pass over 20M x 256 bf16 rows by centre tiles per compute wave (64 centres each),
-    # ms, measured on MI355X (profiles/r3/mb_rr_modes.log): CT <= 2 is HBM-bound, then the MFMA work
-    # grows with CT (under the power-limited clock, not linearly).
-    _CT_COST = {1: 1.72, 2: 1.78, 3: 2.06, 4: 2.45, 5: 2.78}
-
-    def _first_chunk(self, m: int) -> int:
-        """Candidates of the first k-means|| round that take a full K9r pass before the rest are pruned
-        against them (CML_KMEANS_INIT_FIRST caps it, a multiple of 64; default: the first chunk of
-        _candidate_chunks)."""
-        first = self._candidate_chunks(m)[0]
-        cap = os.environ.get("CML_KMEANS_INIT_FIRST")
-        if cap:
-            first = min(first, max(64, int(cap) // 64 * 64), m)
-        return first
-
-    def _rr_max_chunk(self) -> int:
-        """Most centres one K9r launch takes at this row width (320 at Dp = 256 bf16, 128 at Dp = 512:
-        (k/64)·(Dp/32) bounded by the compute waves' VGPRs); 0 when K9r does not apply."""
-        if self._rr_max is None:
-            self._rr_max = 0
-            for c in (320, 256, 192, 128, 64):
-                p = K.plan_assign(1, self.dp, c, fp8=K.is_fp8(self.x))
-                if p.rr_ct > 0 and p.kc == p.kp:
-                    self._rr_max = c
-                    break
-        return self._rr_max
-
-    def _candidate_chunks(self, m: int) -> list:
-        """Split m candidate centres into K9r launches (multiples of 64, at most 256 — 320 where CT = 5
-        exists) minimising the summed pass cost: 520 candidates run as 256 + 264 (two passes, ~27.5)
-        rather than 256 + 256 + 8 (three, ~34)."""
-        big = self._rr_max_chunk() or 256  # 256: K9 launches (no K9r plan at this width)
-        units = -(-m // 64)
-        best = [0.0] + [math.inf] * units  # best[u]: cheapest cover of u units of 64
-        pick = [0] * (units + 1)
-        for u in range(1, units + 1):
-            for c in range(1, big // 64 + 1):
-                v = best[max(0, u - c)] + self._CT_COST.get(c, 20.0)
-                if v < best[u]:
-                    best[u], pick[u] = v, c
-        sizes, u = [], units
-        while u > 0:
-            sizes.append(pick[u] * 64)
-            u = max(0, u - pick[u])
-        sizes.sort(reverse=True)
-        sizes[-1] -= sum(sizes) - m  # the last chunk takes the remainder
-        return [s for s in sizes if s > 0]
 
 
 def assign_gpu(x: torch.Tensor, dp: int, d: int, centers: torch.Tensor, xnorm: Optional[torch.Tensor] = None):

@@ -482,23 +482,43 @@ def plan_assign(n: int, dp: int, k: int, device_index: int = 0, fp8: bool = Fals
                       round_rows=waves * lib.cml_kmeans_assign_tile_rows(dp))
 
 
+_RR_MAX = {}  # rr_max_chunk by (dp, fp8); dropped when a test hook changes the kernel choice
+
+
+def rr_max_chunk(dp: int, fp8: bool = False) -> int:
+    """Most centres one K9r launch takes at this row width (320 at Dp = 256 bf16, 128 at Dp = 512:
+    (k/64)·(Dp/32) bounded by the compute waves' VGPRs); 0 when K9r does not apply."""
+    key = (dp, bool(fp8))
+    if key not in _RR_MAX:
+        _RR_MAX[key] = 0
+        for c in (320, 256, 192, 128, 64):
+            p = plan_assign(1, dp, c, fp8=fp8)
+            if p.rr_ct > 0 and p.kc == p.kp:
+                _RR_MAX[key] = c
+                break
+    return _RR_MAX[key]
+
+
 def set_assign_variant(v: int) -> None:
     """Test hook for the assign kernel choice: 0 automatic (K9r wherever it applies, see set_rr_default, else
     K9 in its default launch shape), 1-3 K9 launch shapes (1 = two 16-row sub-tiles + X double buffer, 2 = one
     sub-tile, 3 = four), 8 forces K9r (register-resident centres + LDS-DMA X ring). Any other value is an error.
     Plans made before a change keep the kernel they were made for."""
     _native.check(_native.kernels().cml_kmeans_set_assign_variant(int(v)), "set_assign_variant")
+    _RR_MAX.clear()
 
 
 def set_rr_default(on: bool) -> None:
     """Whether variant 0 (auto) picks K9r wherever it applies; off, variant 0 is the K9 fallback at every shape."""
     _native.check(_native.kernels().cml_kmeans_set_rr_default(int(bool(on))), "set_rr_default")
+    _RR_MAX.clear()
 
 
 def set_rr_m32(on: bool) -> None:
     """K9r compute waves on 32x32x16 MFMA tiles (even centre-tile counts; CML_KMEANS_RR_M32=1) or the
     16x16x32 form (default, faster on MI355X). Both give the same labels up to the distance rounding."""
     _native.check(_native.kernels().cml_kmeans_set_rr_m32(int(bool(on))), "set_rr_m32")
+    _RR_MAX.clear()
 
 
 def plan_accum(n: int, dp: int, k: int, device_index: int = 0, force: str | None = None,

@@ -165,10 +165,11 @@ def test_precision_modes_cpu():
 
 
 def test_candidate_chunks_cover_and_respect_limits():
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models import kmeans_init
     e = LloydEngine(torch.zeros(10, 4, dtype=torch.float64), 4, 2)
     e.dp = 256
     e.x = torch.zeros(1, 256, dtype=torch.bfloat16)
     for m in (1, 63, 64, 255, 256, 300, 511, 512, 520, 641, 1025, 3000):
-        ch = LloydEngine._candidate_chunks(e, m)
+        ch = kmeans_init._candidate_chunks(e, m)
         assert sum(ch) == m and all(0 < c <= 320 for c in ch)
         assert all(c % 64 == 0 for c in ch[:-1])
