@@ -11,6 +11,12 @@ with the working response z and working weights W computed elementwise on the
 device, one all-reduce of (d+2)² doubles, then a (d+1)×(d+1) solve on the host.
 regParam is Spark's L2 penalty on standardized coefficients (WeightedLeastSquares
 with standardizeFeatures = true).
+
+``family="tweedie"`` (``variancePower``, ``linkPower``) and any family with ``offsetCol`` take ``ops/glr_ops.py``
+instead: one step per iteration that reads the rows once and makes eta, mu, z and the working weight in flight (K33,
+``_native/csrc/glr.hip``, on bf16 device columns of padded width up to 128; the chunked f64 reference form on every
+other column and on CPU frames), with the deviance and Pearson sums of the summary from one more stats-only step.
+The four named families without an offset keep the path above.
 """
 from __future__ import annotations
 
@@ -51,6 +57,14 @@ def _unlink(name, eta):
     if name == "inverse":
         return 1.0 / eta
     return eta * eta
+
+
+def _unlink_any(lnk, eta):
+    """``_unlink`` that also takes tweedie's float link power."""
+    if isinstance(lnk, float):
+        from ..ops import glr_ops as GO
+        return GO.unlink(GO.Spec(GO.FAMILIES.index("tweedie"), 0, 0, 0.0, lnk), eta)
+    return _unlink(lnk, eta)
 
 
 def _deriv(name, mu):
@@ -137,7 +151,7 @@ class GeneralizedLinearRegression(Estimator):
         "featuresCol": ("features", "features column name", str),
         "labelCol": ("label", "label column name", str),
         "predictionCol": ("prediction", "prediction column name", str),
-        "family": ("gaussian", "gaussian | binomial | poisson | gamma", str),
+        "family": ("gaussian", "gaussian | binomial | poisson | gamma | tweedie", str),
         "link": (None, "identity | log | logit | inverse | sqrt (default: the family's canonical link)", None),
         "linkPredictionCol": (None, "link prediction (linear predictor) column name", None),
         "fitIntercept": (True, "whether to fit an intercept term", bool),
@@ -146,10 +160,15 @@ class GeneralizedLinearRegression(Estimator):
         "regParam": (0.0, "L2 regularization parameter (>= 0)", float),
         "weightCol": (None, "weight column name", None),
         "solver": ("irls", "the solver algorithm for optimization (irls)", str),
+        "variancePower": (0.0, "power of the tweedie variance function V(mu) = mu^p (0 or >= 1)", float),
+        "linkPower": (None, "power of the tweedie link mu^linkPower, log at 0 (default: 1 - variancePower)", None),
+        "offsetCol": (None, "offset column name (added to the linear predictor)", None),
     }
 
     def _fit(self, df):
         family = self.getFamily().lower()
+        if family == "tweedie" or (self.isSet("offsetCol") and self.getOrDefault("offsetCol")):
+            return self._fit_step(df, family)
         if family not in _DEFAULT_LINK:
             raise ValueError(f"unsupported family {family!r}")
         link = (self.getOrDefault("link") if self.isSet("link") else None) or _DEFAULT_LINK[family]
@@ -213,6 +232,106 @@ class GeneralizedLinearRegression(Estimator):
         m._summary = GeneralizedLinearRegressionTrainingSummary(it, dev, float(nd[0]), disp, dof, n - (1 if fi else 0))
         return m
 
+    def _fit_step(self, df, family):
+        """family="tweedie", and any family with offsetCol: every IRLS step is one ``glr_ops`` step (K33 on bf16
+        device columns inside its limits, the chunked reference form otherwise) that makes eta, mu, z and the working
+        weight in flight and returns ``[G | stats]``, one all-reduce, then the host solve."""
+        from ..ops import glr_ops as GO
+        from ..ops._fused import use_kernel
+        spec = _spec_of(self, family)
+        x = df._feature_matrix(self.getFeaturesCol())
+        d = x.shape[1]
+        y = df._column_data(self.getLabelCol()).values.to(torch.float64).contiguous()
+        w = df._column_data(self.getOrDefault("weightCol")).values.to(torch.float64).contiguous() \
+            if self.isSet("weightCol") else None
+        off = df._column_data(self.getOrDefault("offsetCol")).values.to(torch.float64).contiguous() \
+            if self.isSet("offsetCol") and self.getOrDefault("offsetCol") else None
+        if family == "tweedie":
+            if 1.0 <= spec.p < 2.0 and bool((y < 0).any()):
+                raise ValueError(f"tweedie family with variancePower {spec.p} needs non-negative labels")
+            if spec.p >= 2.0 and bool((y <= 0).any()):
+                raise ValueError(f"tweedie family with variancePower {spec.p} needs positive labels")
+        else:
+            _check_labels(family, y)
+        comm = df._comm
+        fi, reg, tol = self.getFitIntercept(), self.getRegParam(), self.getTol()
+        kernel = x.is_cuda and d >= 1 and use_kernel(GO, x, None)
+        if kernel:
+            from ..models.kmeans import to_device_matrix
+            x = to_device_matrix(x, d)  # a copy only when the layout is not already the kernel's
+
+        def step(coef, init, gram=True):
+            if kernel:
+                return GO.step(x, d, y, w, off, coef, spec, init, gram)
+            G, st = GO.step_reference(x, d, y, w, off, coef, spec, init)
+            return (G, st) if gram else st
+        m2 = (d + 2) * (d + 2)
+        beta, b0 = np.zeros(d), 0.0
+        it = 0
+        for it in range(1, self.getMaxIter() + 1):
+            G, st = step(np.r_[beta, b0], it == 1)
+            msg = torch.cat([G.reshape(-1), st])
+            comm.allreduce_(msg)
+            nb, n0 = _wls(msg[:m2].reshape(d + 2, d + 2).cpu().numpy(), d, reg, fi)
+            delta = max(float(np.max(np.abs(nb - beta))) if d else 0.0, abs(n0 - b0))
+            beta, b0 = nb, n0
+            if delta < tol:
+                break
+        m = GeneralizedLinearRegressionModel(beta, b0)
+        self._copyValues(m)
+        m._fam, m._lnk, m._iters = family, _link_of(self, family), it
+        m._vp, m._lp = spec.p, spec.lp
+        # training summary: one stats-only step + all-reduce
+        msg = torch.cat([step(np.r_[beta, b0], False, gram=False),
+                         torch.tensor([float(y.numel())], dtype=torch.float64, device=y.device)])
+        comm.allreduce_(msg)
+        dev, pearson, swy, sw, n = (float(v) for v in msg.cpu())
+        # null deviance: the model of the offset and (with fitIntercept) one constant
+        ww = w if w is not None else torch.ones_like(y)
+        oo = off if off is not None else torch.zeros_like(y)
+        if not fi:
+            eta0 = oo
+        elif off is None:
+            eta0 = GO.link(spec, torch.full_like(y, swy / max(sw, 1e-300)))
+        else:
+            c0, eta0 = 0.0, None
+            for _ in range(max(self.getMaxIter(), 1)):
+                t = GO.row_terms(eta0, y, ww, oo, spec)
+                s = torch.stack([(t["wt"] * t["z"]).sum(), t["wt"].sum()])
+                comm.allreduce_(s)
+                new = float(s[0]) / float(s[1])
+                done = abs(new - c0) < tol
+                c0, eta0 = new, oo + new
+                if done:
+                    break
+        nd = GO.row_terms(eta0, y, ww, oo, spec)["dev"].sum().reshape(1)
+        comm.allreduce_(nd)
+        rank = d + (1 if fi else 0)
+        dof = n - rank
+        disp = 1.0 if family in ("binomial", "poisson") else pearson / max(dof, 1.0)
+        m._summary = GeneralizedLinearRegressionTrainingSummary(it, dev, float(nd[0]), disp, dof, n - (1 if fi else 0))
+        return m
+
+
+def _link_of(params, family):
+    """The link's name for a named family (None for tweedie, whose link is its power)."""
+    if family == "tweedie":
+        return None
+    link = (params.getOrDefault("link") if params.isSet("link") else None) or _DEFAULT_LINK[family]
+    if link not in _LINKS:
+        raise ValueError(f"unsupported link {link!r}")
+    return link
+
+
+def _spec_of(params, family):
+    """The ``glr_ops`` spec of an estimator's or a model's params."""
+    from ..ops import glr_ops as GO
+    if family != "tweedie" and family not in _DEFAULT_LINK:
+        raise ValueError(f"unsupported family {family!r}")
+    lp = params.getOrDefault("linkPower") if params.isSet("linkPower") else None
+    return GO.spec(family, _link_of(params, family), float(params.getOrDefault("variancePower")),
+                   None if lp is None else float(lp))
+
 
 class GeneralizedLinearRegressionTrainingSummary:
     def __init__(self, num_iterations, deviance, null_deviance, dispersion, dof, null_dof):
@@ -234,6 +353,8 @@ class GeneralizedLinearRegressionModel(Model):
         self._b0 = float(intercept)
         self._fam = None
         self._lnk = None
+        self._vp = None  # tweedie: the variance power and the link power of the fit
+        self._lp = None
         self._iters = 0
         self._summary = None
 
@@ -260,18 +381,54 @@ class GeneralizedLinearRegressionModel(Model):
         return self._summary
 
     def _family_link(self):
+        """The family and the link's name; for tweedie the link is the float link power."""
         fam = self._fam or self.getFamily().lower()
+        if fam == "tweedie":
+            if self._lp is not None:
+                return fam, float(self._lp)
+            vp = float(self.getOrDefault("variancePower"))
+            lp = self.getOrDefault("linkPower") if self.isSet("linkPower") else None
+            return fam, float(1.0 - vp if lp is None else lp)
         lnk = self._lnk or (self.getOrDefault("link") if self.isSet("link") else None) or _DEFAULT_LINK[fam]
         return fam, lnk
 
-    def predict(self, value) -> float:
+    def _offset_col(self):
+        return self.getOrDefault("offsetCol") if self.isSet("offsetCol") else None
+
+    def predict(self, value, offset: float = 0.0) -> float:
         fam, lnk = self._family_link()
         eta = float(np.dot(as_array(value), self._coef)) + self._b0
-        return float(_unlink(lnk, torch.tensor(eta, dtype=torch.float64)))
+        if self._offset_col():
+            eta += float(offset)
+        return float(_unlink_any(lnk, torch.tensor(eta, dtype=torch.float64)))
+
+    def _transform_step(self, df, x, fam):
+        """tweedie, or offsetCol set: eta and mu from one ``glr_ops`` rows pass (K33 on bf16 device columns inside
+        its limits, the chunked reference form otherwise)."""
+        from ..ops import glr_ops as GO
+        from ..ops._fused import use_kernel
+        d = x.shape[1]
+        spec = _spec_of(self, fam)
+        if fam == "tweedie" and self._lp is not None:
+            spec = spec._replace(p=float(self._vp), lp=float(self._lp))
+        off = df._column_data(self._offset_col()).values.to(torch.float64) if self._offset_col() else None
+        coef = np.r_[self._coef, self._b0]
+        if x.is_cuda and d >= 1 and x.shape[0] and use_kernel(GO, x, None):
+            from ..models.kmeans import to_device_matrix
+            eta, mu, _, _ = GO.rows(to_device_matrix(x, d), d, None, None, off, coef, spec)
+            return eta, mu
+        return GO.rows_reference(x, d, off, coef, spec)
 
     def _transform(self, df):
         x = df._feature_matrix(self.getFeaturesCol())
         fam, lnk = self._family_link()
+        if fam == "tweedie" or self._offset_col():
+            eta, mu = self._transform_step(df, x, fam)
+            out = df
+            if self.isSet("linkPredictionCol") and self.getOrDefault("linkPredictionCol"):
+                out = _replace_col(out, self.getOrDefault("linkPredictionCol"),
+                                   ColumnData(eta.contiguous(), None, T.DoubleType()))
+            return _replace_col(out, self.getPredictionCol(), ColumnData(mu.contiguous(), None, T.DoubleType()))
         eta = glm_ops.linear_predict(x, x.shape[1], torch.as_tensor(np.r_[self._coef, self._b0]))
         out = df
         if self.isSet("linkPredictionCol") and self.getOrDefault("linkPredictionCol"):

@@ -62,6 +62,11 @@
         rise); then K32's loss_grad and scores alone with the issued f64 MFMA rate. --pass-only times K32 alone,
         for sizes at which the dense form does not fit
 
+    python scripts/mb_ml.py glr_step [--rows 10000000] [--dim 64] [--rounds 3]
+        one IRLS step of a poisson / log model on bf16 rows in two forms, interleaved round by round: the fused K33
+        step (tweedie p = 1, log link: the same math) and one iteration of the loop the four named families keep
+        (K24 linear predictor, the torch element-wise passes, K31 weighted Gram); ms, bytes read or written and TB/s
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -914,7 +919,56 @@ def cmd_gram(argv):
     os.environ.pop("CML_GRAM_KERNEL", None)
 
 
-COMMANDS = {"fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_glr_step(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml import glr as GLR
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import glr_ops as GO
+    ap = argparse.ArgumentParser(prog="mb_ml.py glr_step")
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--dim", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args(argv)
+    n, d = a.rows, a.dim
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # in chunks: no n x d f32 temporary
+        x[s0:s0 + step] = torch.randn(min(step, n - s0), d, generator=g, device="cuda").to(torch.bfloat16)
+    coef = torch.cat([0.3 * torch.randn(d, generator=g, device="cuda", dtype=torch.float64) / d ** 0.5,
+                      torch.ones(1, dtype=torch.float64, device="cuda")])
+    y = torch.poisson(torch.exp(glm_ops.linear_predict(x, d, coef)))
+    w = torch.rand(n, generator=g, device="cuda", dtype=torch.float64)
+    xd = to_device_matrix(x, d)
+    spec = GO.spec("tweedie", None, 1.0, 0.0)
+    xbytes = x.numel() * x.element_size()
+
+    def fused():
+        return GO.step(xd, d, y, w, None, coef, spec, False)
+
+    def loop():  # one iteration of ml/glr.py's loop for family="poisson": eta, mu, z, wt, then the Gram
+        eta = glm_ops.linear_predict(x, d, coef)
+        mu = GLR._project("poisson", GLR._unlink("log", eta))
+        dmu = GLR._deriv("log", mu)
+        z = eta + (y - mu) * dmu
+        wt = w / (dmu * dmu * GLR._variance("poisson", mu))
+        return glm_ops.gram(x, d, z, wt)
+
+    # bytes: K33 reads the rows once and y, w; the loop reads the rows twice and writes / reads the n-vectors of its
+    # 9 element-wise kernels (3 with one operand, 6 with two, one result each: 24 vector passes) besides K24's eta and
+    # K31's z, wt
+    fused_bytes = xbytes + 2 * 8 * n
+    loop_bytes = 2 * xbytes + (1 + 24 + 2) * 8 * n
+    Gf, Gl = fused()[0], loop()
+    print(f"max rel diff of G between the two forms: "
+          f"{float(((Gf - Gl).abs() / Gl.abs().clamp(min=1e-300)).max()):.2e}", flush=True)
+    for r in range(a.rounds):
+        for name, fn, nbytes in (("K33 step", fused, fused_bytes), ("K24 + torch + K31", loop, loop_bytes)):
+            ms = best_ms(fn, reps=3)
+            print(f"round {r} glr step {n}x{d} bf16 [{name}]: {ms:.2f} ms, {nbytes / 1e9:.2f} GB, "
+                  f"{nbytes / ms / 1e9:.3f} TB/s ({xbytes / ms / 1e9:.3f} TB/s counting the rows once)", flush=True)
+
+
+COMMANDS = {"glr_step": cmd_glr_step, "fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
