@@ -67,6 +67,12 @@
         step (tweedie p = 1, log link: the same math) and one iteration of the loop the four named families keep
         (K24 linear predictor, the torch element-wise passes, K31 weighted Gram); ms, bytes read or written and TB/s
 
+    python scripts/mb_ml.py nb [--rows 10000000] [--dim 64] [--classes 2 16] [--rounds 2] [--ops-only]
+        the two row passes of naive Bayes on bf16 rows, K34 against the chunked reference form (ms, bytes, TB/s), then
+        NaiveBayes fit and transform (multinomial and gaussian) in three forms, interleaved round by round: the
+        kernel, the reference form (CML_NB_KERNEL=0) and the dense form on an f32 frame of the same values (ms, peak
+        allocation rise); dense steps whose f64 temporaries would not fit are skipped
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -968,7 +974,91 @@ def cmd_glr_step(argv):
                   f"{nbytes / ms / 1e9:.3f} TB/s ({xbytes / ms / 1e9:.3f} TB/s counting the rows once)", flush=True)
 
 
-COMMANDS = {"glr_step": cmd_glr_step, "fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_nb(argv):
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ml.classification import NaiveBayes
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import nb_ops as NO
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.sql import SparkSession
+    ap = argparse.ArgumentParser(prog="mb_ml.py nb")
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--dim", type=int, default=64)
+    ap.add_argument("--classes", type=int, nargs="+", default=[2, 16])
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--ops-only", action="store_true", help="time the two passes alone, not the estimator")
+    ap.add_argument("--dense-limit-gb", type=float, default=24.0,
+                    help="skip a dense-form step whose largest f64 temporary would pass this size")
+    a = ap.parse_args(argv)
+    n, d = a.rows, a.dim
+    spark = SparkSession({"spark.master": "mi355x", "spark.app.name": "mb-nb"})
+    g = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+    step = 1 << 22
+    for s0 in range(0, n, step):  # counts 0 .. 8 in chunks: exact in bf16, and valid for every model type but bernoulli
+        x[s0:s0 + step] = torch.randint(0, 9, (min(step, n - s0), d), generator=g, device="cuda").to(torch.bfloat16)
+    xd = to_device_matrix(x, d)
+    xbytes = x.numel() * x.element_size()
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3, out
+
+    for C in a.classes:
+        y = torch.randint(0, C, (n,), generator=g, device="cuda").to(torch.float64)
+        lab = y.to(torch.int32)
+        shift = torch.rand(C, d, generator=g, device="cuda", dtype=torch.float64) * 8.0
+        W = torch.randn(C, d, generator=g, device="cuda", dtype=torch.float64) * 0.05
+        b = torch.zeros(C, dtype=torch.float64, device="cuda")
+        iv = torch.full((C, d), 0.2 / d, dtype=torch.float64, device="cuda")
+        ops = (("moments, pass 1", lambda: NO.moments(xd, d, lab, None, C, None, False),
+                lambda: NO.moments_reference(x, d, lab, None, C), xbytes + 4 * n),
+               ("moments, pass 2 (shift, second)", lambda: NO.moments(xd, d, lab, None, C, shift, True),
+                lambda: NO.moments_reference(x, d, lab, None, C, shift), xbytes + 4 * n),
+               ("scores, linear", lambda: NO.scores(xd, d, "linear", W, b),
+                lambda: NO.scores_reference(x, d, "linear", W, b), xbytes + (2 * C + 1) * 8 * n),
+               ("scores, gaussian", lambda: NO.scores(xd, d, "gaussian", shift, b, iv),
+                lambda: NO.scores_reference(x, d, "gaussian", shift, b, iv), xbytes + (2 * C + 1) * 8 * n))
+        for name, kern, ref, nbytes in ops:
+            for r in range(a.rounds):
+                km, rm = best_ms(kern, reps=3), best_ms(ref, reps=2)
+                print(f"round {r} nb {n}x{d} bf16 C={C} [{name}]: K34 {km:.2f} ms ({nbytes / 1e9:.2f} GB, "
+                      f"{nbytes / km / 1e9:.3f} TB/s), reference form {rm:.2f} ms", flush=True)
+        if a.ops_only:
+            continue
+        frames = {"bf16": spark.createDataFrameFromTensors({"features": x, "label": y}),
+                  "f32": None}
+        for mt in ("multinomial", "gaussian"):
+            for r in range(a.rounds):
+                for form in ("kernel", "reference", "dense f32"):
+                    os.environ["CML_NB_KERNEL"] = "0" if form == "reference" else "1"
+                    if form == "dense f32":
+                        if 4 * n * d * 8 / 1e9 > a.dense_limit_gb:
+                            print(f"round {r} nb {mt} C={C} [{form}]: skipped (fit temporaries)", flush=True)
+                            continue
+                        if frames["f32"] is None:
+                            frames["f32"] = spark.createDataFrameFromTensors({"features": x.to(torch.float32),
+                                                                              "label": y})
+                    df = frames["f32" if form == "dense f32" else "bf16"]
+                    torch.cuda.reset_peak_memory_stats()
+                    base = torch.cuda.memory_allocated()
+                    fit_ms, m = wall(lambda: NaiveBayes(modelType=mt).fit(df))
+                    rise = torch.cuda.max_memory_allocated() - base
+                    if form == "dense f32" and mt == "gaussian" and n * C * d * 8 / 1e9 > a.dense_limit_gb:
+                        tr = "transform skipped (n x C x d f64)"
+                    else:
+                        tr_ms, out = wall(lambda: m.transform(df)._column_data("prediction").values)
+                        tr = f"transform {tr_ms:.1f} ms"
+                        del out
+                    print(f"round {r} nb {mt} {n}x{d} C={C} [{form}]: fit {fit_ms:.1f} ms "
+                          f"(peak rise {rise / xbytes:.2f} x the bf16 rows), {tr}", flush=True)
+        os.environ.pop("CML_NB_KERNEL", None)
+        del frames
+    spark.stop()
+
+
+COMMANDS = {"nb": cmd_nb, "glr_step": cmd_glr_step, "fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
