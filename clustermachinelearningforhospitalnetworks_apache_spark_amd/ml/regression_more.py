@@ -5,8 +5,12 @@ model is the MLlib estimator for durations with right-censoring (patients still 
 isotonic regression fits a monotone dose-response curve (e.g. LOS vs occupancy). MI355X-first:
 
 * AFTSurvivalRegression: Weibull AFT negative log-likelihood over the standardized features.
-  Each L-BFGS evaluation is two device GEMVs over the HBM-resident shard (margins, then
-  Xᵀ·residual) + one all-reduce of the (d+3)-vector; the optimizer runs on the host.
+  Each L-BFGS evaluation is one all-reduce of the (d+3)-vector ``[Xᵀr | Σr | Σs | Σl]``; the
+  optimizer runs on the host. A bf16 device column is read as stored, once per evaluation, by
+  K35 (``ops/aft_ops.loss_grad``: padded width 16..512); an e4m3 column, a wider one and
+  ``CML_AFT_KERNEL=0`` take the chunked f64 form of the same module, which never holds an
+  n x d copy either. f32 / f64 columns and CPU frames keep the dense form: two GEMVs over the
+  f64 rows (margins, then Xᵀ·residual). ``transform`` makes the same three-way choice.
 * IsotonicRegression: the (feature, label, weight) triples are gathered once, sorted on the
   device, equal features pooled, and pool-adjacent-violators runs in one host pass (O(n));
   prediction is one device ``searchsorted`` + linear interpolation.
@@ -20,6 +24,7 @@ import numpy as np
 import torch
 
 from ..models.optim import lbfgs
+from ..ops import _fused, aft_ops
 from ..sql import types as T
 from ..sql.column import ColumnData
 from . import util as U
@@ -44,6 +49,11 @@ _AFT_PARAMS = {
 }
 
 
+def _stored_form(x: torch.Tensor) -> bool:
+    """Whether the rows ``x`` go to ``ops/aft_ops`` as stored: a bf16 or e4m3 device column with a feature."""
+    return x.is_cuda and x.shape[1] >= 1 and x.dtype in (torch.bfloat16, torch.float8_e4m3fn)
+
+
 class AFTSurvivalRegression(Estimator):
     """Weibull accelerated failure time model: log T = β·x + b + σ·ε with ε extreme-value
     distributed. Minimises the mean negative log-likelihood over θ = (β, b, log σ)
@@ -56,7 +66,10 @@ class AFTSurvivalRegression(Estimator):
 
     def _fit(self, df):
         from .classification_more import _std
-        x = df._feature_matrix(self.getFeaturesCol()).to(torch.float64)
+        x = df._feature_matrix(self.getFeaturesCol())
+        stored = _stored_form(x)  # a bf16 / e4m3 device column is read as it is stored, never widened whole
+        if not stored:
+            x = x.to(torch.float64)
         d = x.shape[1]
         t = df._column_data(self.getLabelCol()).values.to(torch.float64)
         delta = df._column_data(self.getCensorCol()).values.to(torch.float64)
@@ -76,11 +89,20 @@ class AFTSurvivalRegression(Estimator):
         comm.allreduce_(cnt)
         N = max(float(cnt.item()), 1.0)
         dev = x.device
+        kernel = stored and _fused.use_kernel(aft_ops, x, None)
+        if kernel:
+            from ..models.kmeans import to_device_matrix
+            x = to_device_matrix(x, d)  # a copy only when the layout is not already the kernel's
 
         def fg(p):
             beta = np.where(active, p[:d] / sd, 0.0)
             b = p[d] if fi else 0.0
             ls = p[d + 1]
+            if stored:
+                coef = torch.as_tensor(np.r_[beta, b, ls], device=dev)
+                msg = aft_ops.loss_grad(x, d, logt, delta, coef) if kernel else \
+                    aft_ops.loss_grad_reference(x, d, logt, delta, coef)
+                return finish(msg)
             sigma = math.exp(ls)
             m = x @ torch.as_tensor(beta, device=dev) + b
             eps = (logt - m) / sigma
@@ -89,6 +111,9 @@ class AFTSurvivalRegression(Estimator):
             r = (delta - ee) / sigma  # dℓ/dm
             msg = torch.cat([x.T @ r, r.sum().reshape(1), (delta + (delta - ee) * eps).sum().reshape(1),
                              loss.reshape(1)])
+            return finish(msg)
+
+        def finish(msg):
             comm.allreduce_(msg)
             o = msg.cpu().numpy()
             g = np.zeros(d + 2)
@@ -129,6 +154,13 @@ class AFTSurvivalRegressionModel(Model):
         return int(self._coef.size)
 
     def _lam(self, x: torch.Tensor) -> torch.Tensor:
+        if _stored_form(x):
+            d = x.shape[1]
+            coef = torch.as_tensor(np.r_[self._coef, self._icpt, math.log(self._scale)], device=x.device)
+            if _fused.use_kernel(aft_ops, x, None):
+                from ..models.kmeans import to_device_matrix
+                return torch.exp(aft_ops.rows(to_device_matrix(x, d), d, coef))
+            return torch.exp(aft_ops.rows_reference(x, d, coef))
         return torch.exp(x.to(torch.float64) @ torch.as_tensor(self._coef, device=x.device) + self._icpt)
 
     def _qfac(self) -> np.ndarray:

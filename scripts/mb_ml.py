@@ -73,6 +73,12 @@
         kernel, the reference form (CML_NB_KERNEL=0) and the dense form on an f32 frame of the same values (ms, peak
         allocation rise); dense steps whose f64 temporaries would not fit are skipped
 
+    python scripts/mb_ml.py aft [--shapes 10000000x64 4000000x256] [--rounds 3] [--dense-limit-gb 24]
+        one L-BFGS evaluation of AFTSurvivalRegression on bf16 rows in three forms, interleaved round by round: the
+        K35 kernel, the chunked reference form and the dense form of f32 / f64 columns (two GEMVs on an f64 copy
+        of the rows and the element-wise passes between them; skipped where the copy would not fit); then K35's rows
+        form; ms, bytes read and their rate against the 6.3 TB/s copy rate
+
 ``--scale`` multiplies every row count (e.g. 0.05 for a quick check).
 """
 import argparse
@@ -1058,7 +1064,66 @@ def cmd_nb(argv):
     spark.stop()
 
 
-COMMANDS = {"nb": cmd_nb, "glr_step": cmd_glr_step, "fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
+def cmd_aft(argv):
+    import math
+
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.models.kmeans import to_device_matrix
+    from clustermachinelearningforhospitalnetworks_apache_spark_amd.ops import aft_ops as AO
+    ap = argparse.ArgumentParser(prog="mb_ml.py aft")
+    ap.add_argument("--shapes", nargs="+", default=["10000000x64", "4000000x256"])
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--dense-limit-gb", type=float, default=24.0, help="skip the dense form above this f64 copy")
+    a = ap.parse_args(argv)
+    copy_rate = 6.3e12  # B/s, the copy rate PARITY.md measures against
+    for shape in a.shapes:
+        n, d = (int(v) for v in shape.split("x"))
+        g = torch.Generator(device="cuda").manual_seed(1)
+        x = torch.empty(n, d, dtype=torch.bfloat16, device="cuda")
+        step = 1 << 22
+        for s0 in range(0, n, step):  # in chunks: no n x d f32 temporary
+            x[s0:s0 + step] = torch.randn(min(step, n - s0), d, generator=g, device="cuda").to(torch.bfloat16)
+        beta = 0.3 * torch.randn(d, generator=g, device="cuda", dtype=torch.float64) / d ** 0.5
+        ls = math.log(0.9)
+        coef = torch.cat([beta, torch.tensor([0.8, ls], dtype=torch.float64, device="cuda")])
+        logt = AO.rows_reference(x, d, coef) - 0.8 + 0.7 * torch.log(
+            -torch.log1p(-torch.rand(n, generator=g, device="cuda", dtype=torch.float64)))
+        delta = (torch.rand(n, generator=g, device="cuda") < 0.7).to(torch.float64)
+        xd = to_device_matrix(x, d)
+        xbytes = x.numel() * x.element_size()
+        x64 = x.to(torch.float64) if 8 * n * d / 1e9 <= a.dense_limit_gb else None
+
+        def dense():  # fg of the f32 / f64 columns in ml/regression_more.py
+            sigma = math.exp(ls)
+            m = x64 @ beta + 0.8
+            eps = (logt - m) / sigma
+            ee = torch.exp(eps)
+            loss = (delta * ls - delta * eps + ee).sum()
+            r = (delta - ee) / sigma
+            return torch.cat([x64.T @ r, r.sum().reshape(1), (delta + (delta - ee) * eps).sum().reshape(1),
+                              loss.reshape(1)])
+
+        # bytes: K35 and the reference form read the rows once and logt, delta; the dense form reads its f64 copy twice
+        # and the n-vectors of its 11 element-wise and 3 sum kernels (34 vector passes) besides the two GEMVs' m and r
+        forms = [("K35 loss_grad", lambda: AO.loss_grad(xd, d, logt, delta, coef), xbytes + 16 * n),
+                 ("reference form", lambda: AO.loss_grad_reference(x, d, logt, delta, coef), xbytes + 16 * n)]
+        if x64 is not None:
+            forms.append(("dense f64", dense, 2 * 8 * n * d + (34 + 2) * 8 * n))
+            ref = dense()
+            got = forms[0][1]()
+            print(f"aft {n}x{d}: max rel diff of the message, K35 vs dense: "
+                  f"{float(((got - ref).abs() / ref.abs().clamp(min=1e-300)).max()):.2e}", flush=True)
+        forms.append(("K35 rows, eta only", lambda: AO.rows(xd, d, coef), xbytes + 8 * n))
+        forms.append(("K35 rows with terms", lambda: AO.rows(xd, d, coef, logt, delta), xbytes + 48 * n))
+        for r in range(a.rounds):
+            for name, fn, nbytes in forms:
+                ms = best_ms(fn, reps=3)
+                print(f"round {r} aft {n}x{d} bf16 [{name}]: {ms:.2f} ms, {nbytes / 1e9:.2f} GB, "
+                      f"{nbytes / ms / 1e9:.3f} TB/s = {100 * nbytes / (ms * 1e-3) / copy_rate:.0f} % of the copy rate "
+                      f"(floor {1e3 * nbytes / copy_rate:.2f} ms)", flush=True)
+        del x, xd, x64, logt, delta, forms
+
+
+COMMANDS = {"aft": cmd_aft, "nb": cmd_nb, "glr_step": cmd_glr_step, "fm": cmd_fm, "gram": cmd_gram, "mlp": cmd_mlp, "lda": cmd_lda, "gmm": cmd_gmm, "bisecting": cmd_bisecting, "silhouette": cmd_silhouette,"multinomial": cmd_multinomial, "glm": cmd_glm, "glm-fp8": cmd_glm_fp8, "logreg": cmd_logreg, "trees": cmd_trees,
             "tree-transform": cmd_tree_transform}
 
 if __name__ == "__main__":
