@@ -535,7 +535,12 @@ CML_API int cml_kmeans_cert_moves(const void* X, int xf64, long long n, long lon
                                   int* hist, int* seg, int* cursor, int* perm, double* P_hi, double* P_lo,
                                   double* S_hi, double* S_lo, int* cnt, const double* C_cur, double* C_next,
                                   double* shift2, void* stream) {
-  if (d <= 0 || k <= 0) return (int)hipErrorInvalidValue;
+  // cert_hist asks for 2·k and cert_scatter for 4·k ints of dynamic LDS. The engine brings k <= 320 here:
+  // precision "screen" needs LloydEngine.screen_applies (models/kmeans.py), a K9r plan that holds every
+  // centre in one launch (plan_assign's kc == kp from cml_kmeans_assign_rr_plan), and rr::plan_ct
+  // (kmeans_rr.h) grants none beyond five 64-centre tiles (ct > 5 -> 0) — 320 centres, 5 KiB. Other
+  // callers are refused before any launch once 4·k ints pass the 64 KiB a kernel gets by default.
+  if (d <= 0 || k <= 0 || k > 4096) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const int ns = cml_kmeans_cert_slices(k);
   if (n > 0) {

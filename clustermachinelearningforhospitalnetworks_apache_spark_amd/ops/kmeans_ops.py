@@ -1461,15 +1461,18 @@ def cert_slices(k: int) -> int:
 
 def cert_moves(x: torch.Tensor, k: int, mv_row, mv_old, mv_new, m_dev, hist, seg, cursor, perm, P_hi, P_lo,
                S_hi, S_lo, cnt, stream=None, C_cur: torch.Tensor | None = None,
-               C_next: torch.Tensor | None = None) -> None:
+               C_next: torch.Tensor | None = None, shift2: torch.Tensor | None = None) -> None:
     """Apply the label moves to the double-double cluster sums S_hi / S_lo and the int32 counts; with
-    ``C_next`` (one rank) also the centre update C_next = S_hi / count (an empty cluster keeps C_cur)."""
+    ``C_next`` (one rank) also the centre update C_next = S_hi / count (an empty cluster keeps C_cur)
+    and, with ``shift2`` (f64 [k]), every centre's squared move ||C_next - C_cur||²."""
+    if shift2 is not None and (C_next is None or shift2.dtype != torch.float64 or shift2.numel() < int(k)):
+        raise ValueError("cert_moves: shift2 needs C_next and k f64 entries")
     n, d = int(x.shape[0]), int(S_hi.shape[1])
     _native.check(_native.kernels().cml_kmeans_cert_moves(
         x.data_ptr(), int(x.dtype == torch.float64), n, x.stride(0), d, int(k), mv_row.data_ptr(), mv_old.data_ptr(),
         mv_new.data_ptr(), m_dev.data_ptr(), hist.data_ptr(), seg.data_ptr(), cursor.data_ptr(), perm.data_ptr(),
         P_hi.data_ptr(), P_lo.data_ptr(), S_hi.data_ptr(), S_lo.data_ptr(), cnt.data_ptr(), _ptr(C_cur),
-        _ptr(C_next), 0, _native.stream_ptr(stream)), "kmeans_cert_moves")
+        _ptr(C_next), _ptr(shift2), _native.stream_ptr(stream)), "kmeans_cert_moves")
 
 
 def sum_exact(v: torch.Tensor) -> torch.Tensor:
