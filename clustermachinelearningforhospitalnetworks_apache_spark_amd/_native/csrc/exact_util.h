@@ -31,6 +31,15 @@ __device__ __forceinline__ float f32_dn(double v) {
   if ((double)f > v) f = nextafterf(f, 0.0f);
   return f;
 }
+// f64 -> f32 -> bf16, each to nearest even: the rounding of a double that the host forms (torch) apply. Written
+// as (__bf16)(float)v the two conversions are folded into one rounding from f64 (an f32 rounded to odd, then
+// bf16), which gives the other neighbour where the f32 value falls on a bf16 tie; the empty asm keeps the f32
+// rounding a step of its own. For a widened f32 value the first step is exact either way.
+__device__ __forceinline__ u16 f64_to_bf16_via_f32(double v) {
+  float f = (float)v;
+  asm volatile("" : "+v"(f));
+  return f32_to_bf16(f);
+}
 // a fold of d f64 products differs from the real squared distance by far less than this (relative)
 constexpr double kFoldMargin = 1e-10;
 

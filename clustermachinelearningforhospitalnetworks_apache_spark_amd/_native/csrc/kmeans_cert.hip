@@ -229,9 +229,9 @@ __global__ __launch_bounds__(1024) void split_centres_kernel(const double* __res
       u16 hb = 0, lb = 0;
       if (j < k && t < d) {
         const double v = C[(long long)j * d + t];
-        hb = f32_to_bf16((float)v);
+        hb = f64_to_bf16_via_f32(v);
         const double r1 = v - (double)bf16_to_f32(hb);
-        lb = f32_to_bf16((float)r1);
+        lb = f64_to_bf16_via_f32(r1);
         const double lv = (double)bf16_to_f32(lb);
         const double rc = r1 - lv;
         a2 = __fma_rn(lv, lv, a2);

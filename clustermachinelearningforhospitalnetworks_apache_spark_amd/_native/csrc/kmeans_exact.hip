@@ -348,7 +348,7 @@ __global__ __launch_bounds__(kThreads) void to_bf16_err_kernel(const T* __restri
       u16 b = 0;
       if (t < d) {
         const double v = (double)X[r * ldx + t];
-        b = f32_to_bf16((float)v);  // f64 -> f32 -> bf16: a double rounding, covered by the exact error below
+        b = f64_to_bf16_via_f32(v);  // f64 -> f32 -> bf16: a double rounding, covered by the exact error below
         const double e = v - (double)bf16_to_f32(b);
         e2 = __fma_rn(e, e, e2);
       }
@@ -400,9 +400,9 @@ __global__ __launch_bounds__(kThreads) void to_bf16_split_kernel(const T* __rest
           const int t = t0 + u;
           if (t < d) {
             const double v = (double)xv8[u];
-            const u16 hb = f32_to_bf16((float)v);
+            const u16 hb = f64_to_bf16_via_f32(v);
             const double r1 = v - (double)bf16_to_f32(hb);
-            const u16 lb = f32_to_bf16((float)r1);
+            const u16 lb = f64_to_bf16_via_f32(r1);
             const double lv = (double)bf16_to_f32(lb);
             const double rx = r1 - lv;
             a2 = __fma_rn(lv, lv, a2);

@@ -34,6 +34,9 @@ def test_exact_assign_matches_f64_reference(n, d, k, dt):
         m, i = ref.min(1)
         torch.testing.assert_close(best, m, rtol=1e-12, atol=1e-9)
         assert float((lab.long() != i).float().mean()) == 0.0
+    else:  # too large for the broadcast form: the host twin (the same fold and ties, test_exact_oracle.py)
+        hl, hb = K.assign_reference(x.cpu(), c.cpu())
+        assert torch.equal(lab.long().cpu(), hl) and torch.equal(best.cpu(), hb)
     lab2, best2 = K.exact_assign(x, c)
     assert torch.equal(lab, lab2) and torch.equal(best, best2)
 
